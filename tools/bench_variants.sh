@@ -9,7 +9,7 @@ for v in "$@"; do
   i=$((i+1))
   args=""
   [ "$v" != "-" ] && for o in $v; do args="$args --option $o"; done
-  timeout -k 10 300 python3 bench.py --no-cpu --workload paths --steps 10 --warmup 2 $args > $out/v$i.json 2> $out/v$i.err || exit 1
+  timeout -k 10 300 python3 bench.py --full --no-cpu --workload paths --steps 10 --warmup 2 $args > $out/v$i.json 2> $out/v$i.err || exit 1
   python3 - "$out/v$i.json" "$v" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ for v in "$@"; do
   i=$((i+1))
   args=""
   [ "$v" != "-" ] && for o in $v; do args="$args --option $o"; done
-  timeout -k 10 300 python3 bench.py --no-cpu --steps 20 --warmup 3 $args > $out/g$i.json 2> $out/g$i.err || exit 1
+  timeout -k 10 300 python3 bench.py --full --no-cpu --steps 20 --warmup 3 $args > $out/g$i.json 2> $out/g$i.err || exit 1
   python3 - "$out/g$i.json" "$v" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

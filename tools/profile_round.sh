@@ -12,7 +12,7 @@ bash tools/gpu_profile.sh $tag
 stats() {  # name, bench args...
   local name=$1; shift
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_$name -o run -- \
-    python3 bench.py --no-cpu "$@" > $out/${name}_bench.json 2> $out/${name}.err
+    python3 bench.py --full --no-cpu "$@" > $out/${name}_bench.json 2> $out/${name}.err
   cp $out/kt_$name/run_kernel_stats.csv $out/${name}_kernel_stats.csv
   rm -rf $out/kt_$name
 }

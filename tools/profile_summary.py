@@ -69,8 +69,8 @@ def main():
             "write_bytes": (sum(w) / len(w) * 1024) if w else None,
         })
     out = {"tag": tag, "bench": bench, "query_kernels": kernels,
-           "note": "kernel stats from rocprofv3 --kernel-trace --stats of bench.py --no-cpu --steps 5 --warmup 1; "
-                   "FETCH_SIZE/WRITE_SIZE from separate --pmc passes (bench.py --steps 2 --warmup 1), per launch; "
+           "note": "kernel stats from rocprofv3 --kernel-trace --stats of bench.py --full --no-cpu --steps 5 --warmup 1; "
+                   "FETCH_SIZE/WRITE_SIZE from separate --pmc passes (bench.py --full --steps 2 --warmup 1), per launch; "
                    "fetch_bytes_x2 applies the gfx950 wide-read correction"}
     outdir.mkdir(exist_ok=True)
     (outdir / f"{tag}_summary.json").write_text(json.dumps(out, indent=1) + "\n")

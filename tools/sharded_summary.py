@@ -9,7 +9,7 @@ Projection model (stated in the output):
                + exchanges: N_coll collectives (counted by the engine, nbg_timing.comm_calls) x
                  (L1 + dL), plus the rank's exchange bytes over its W - 1 xGMI links at B_link
   where the one-rank numbers come from the SHARDED algorithm run through a real one-rank RCCL
-  communicator (bench.py --comm-single, tools/kt_timeline.sh ... --comm-single): K1 = its kernels
+  communicator (bench.py --full --comm-single, tools/kt_timeline.sh ... --comm-single): K1 = its kernels
   without the RCCL ones, L1 = one RCCL call on the engine stream (its kernel + the idle gap before
   the next launch), measured; dL = the extra latency of a W-rank exchange over xGMI, ASSUMED
   (a one-GPU lease cannot measure it).
@@ -109,7 +109,7 @@ def main():
         proj.append((w, ncoll, k_us, c_us, host_us, k_us + c_us + host_us))
     md += ["", "## Projected per-GPU C3 query time at W GPUs", "",
            "The one-rank numbers are the sharded algorithm run through a real one-rank RCCL communicator",
-           f"(`bench.py --comm-single`: {one_wall:.0f} us/query wall, digest {bench['parity'].get('status')};",
+           f"(`bench.py --full --comm-single`: {one_wall:.0f} us/query wall, digest {bench['parity'].get('status')};",
            f"kernel timeline: {busy:.0f} us busy, of it {rk_us:.0f} us in {n_rccl} RCCL kernels).", "",
            f"* kernels = {fixed_us:.0f} us that do not shrink with W ({', '.join(FIXED)}) + the other",
            f"  {k1_us - fixed_us:.0f} us of the one-rank sharded query's kernels (RCCL's excluded) x the slowest",
