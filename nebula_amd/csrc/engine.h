@@ -578,9 +578,6 @@ struct Ctx {
   Timing timing;
   hipEvent_t ev[8] = {};
   DevBuf ws_tile_rows;  // k_expand: frontier entry of each tile's first slot
-  std::string bu_kernel_name, bu_rest_name;  // rocprof names of the last bottom-up launch
-  bool bu_rest_rec = false;                  // ... whose rest pass read the rest records
-  uint64_t bu_od_bytes = 0;                  // ... out-degree bytes its first pass read (non-final hop)
   // deferred kernel timing: event pairs recorded around expansion launches and read once the
   // query's stream has drained, so timing never makes the host wait on a launch
   struct PendingTime {

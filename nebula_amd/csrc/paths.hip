@@ -3679,7 +3679,7 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
   hipEventElapsedTime(&ms, c.ev[0], c.ev[1]);
   c.timing.total_ms = ms;
 
-  auto* h = new HostRows();
+  auto h = std::make_unique<HostRows>();
   for (int k = 0; k < 3; k++) {
     h->types.push_back(NBG_T_VID);
     h->host.emplace_back(npairs * 8 + 8);
@@ -3694,7 +3694,7 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
   h->path_offsets = std::move(hoff);
   h->path_vids = std::move(hpath);
   if (h->path_vids.empty()) h->path_vids.push_back(0);  // non-null pointer for an empty result
-  fill_rows(out, h, int64_t(npairs), false);
+  fill_rows(out, std::move(h), int64_t(npairs), false);
   out->edges_scanned = c.timing.edges_scanned;
   return NBG_OK;
 }

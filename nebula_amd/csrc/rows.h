@@ -1,6 +1,7 @@
 // rows.h -- host-side owner of a result handed out through nbg_rows (freed by nbg_rows_free).
 #pragma once
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "engine.h"
@@ -27,7 +28,9 @@ struct HostRows {
   std::vector<uint8_t*> vertex_pres;
 };
 
-inline void fill_rows(nbg_rows* out, HostRows* h, int64_t nrows, bool on_device) {
+// hands the rows to `out` (nbg_rows_free / free_rows_impl deletes them); until this call the
+// caller's unique_ptr frees them on every exit, a throw included
+inline void fill_rows(nbg_rows* out, std::unique_ptr<HostRows> h, int64_t nrows, bool on_device) {
   memset(out, 0, sizeof(*out));
   out->n_rows = nrows;
   out->n_cols = int32_t(h->types.size());
@@ -44,7 +47,6 @@ inline void fill_rows(nbg_rows* out, HostRows* h, int64_t nrows, bool on_device)
   out->failed_codes = h->failed_codes.empty() ? nullptr : h->failed_codes.data();
   out->path_offsets = h->path_offsets.empty() ? nullptr : h->path_offsets.data();
   out->path_vids = h->path_vids.empty() ? nullptr : h->path_vids.data();
-  out->_impl = h;
   h->vertex_cols.clear();
   h->vertex_str_off.clear();
   h->vertex_pres.clear();
@@ -58,6 +60,7 @@ inline void fill_rows(nbg_rows* out, HostRows* h, int64_t nrows, bool on_device)
   out->vertex_cols = h->vertex_cols.empty() ? nullptr : h->vertex_cols.data();
   out->vertex_str_offsets = h->vertex_str_off.empty() ? nullptr : h->vertex_str_off.data();
   out->vertex_col_present = h->vertex_pres.empty() ? nullptr : h->vertex_pres.data();
+  out->_impl = h.release();
 }
 
 }  // namespace nbg

@@ -686,6 +686,61 @@ __device__ inline void block_store_partials(const unsigned long long* v, int k, 
     partials[size_t(threadIdx.x) * kAggBlocks + blockIdx.x] = s;  // slot-major: coalesced reduce
   }
 }
+// ---- a GO query's counter block --------------------------------------------------------------
+// Ctx::ws_counters (device, "Kd" in the kernels) and its pinned host mirror Ctx::host_counters
+// (Counters::d / ::h): 256 words of 8 B, then shards 1 .. kSumShards - 1 of every word
+// (block_add_sums), kShardStride words apart.  Words [0, kSpecBase) are the hop counters below,
+// reused from hop to hop; [kSpecBase, 256) the speculated hops' blocks (SpecWord).
+namespace {
+// the eight counters a bottom-up hop's two passes reduce into their `out` block
+enum HopWord : int {
+  kHopFound = 0,      // rows found (bits set in the next frontier)
+  kHopDegSum = 1,     // ... their out-degree sum (non-final hops)
+  kHopSlabWords = 2,  // slab words the first pass read
+  kHopPending = 3,    // rows left pending for the rest pass
+  kHopEntries = 4,    // adjacency entries the rest pass read
+  kHopValues = 5,     // predicate values the rest pass read ([6] / [7]: probe statistics)
+  kHopWords = 8,
+};
+enum CounterWord : int {
+  // a list length, counted by atomics: the frontier list (k_list_starts, k_starts_bits, k_compact,
+  // k_bits_compact<0>) or the DISTINCT _dst output of a host-chosen final bottom-up hop.  A
+  // host-chosen non-final bottom-up hop reduces its HopWord block into [kCntList, kHopWords).
+  kCntList = 0,
+  kCntRows = 2,       // rows the final expansion kept (EXP_ROWS)
+  kCntWhereErr = 4,   // WHERE evaluation errors (ExpandArgs::err)
+  kCntYieldErr = 5,   // YIELD evaluation errors (k_materialize)
+  kCntFinalHop = 8,   // [8, 16): the HopWord block of a host-chosen final bottom-up hop
+  // a compaction's sums (k_compact, k_starts_bits, k_or_segments_bits), sharded when the
+  // compaction runs with shards > 1:
+  kCntSet = 12,     // vertices set in the byte map (found)
+  kCntDegSum = 13,  // out-degree sum of the kept vertices (the next hop's E)
+  kCntKept = 14,    // kept vertices (= the list length, also when no list is written)
+  // go_rep1: this rank's share of the whole-space compaction (k_compact's own_lo / own_hi)
+  kCntOwnKept = 15,
+  kCntOwnDegSum = 16,
+  kCntRed = 24,       // scratch of the cross-rank sums made through the host (allsum)
+  kCntHop1Rows = 30,  // degree sum over every start, duplicates included (k_starts_degree, k_starts_small)
+  kCntStartWords = 32,  // the words a fetch behind the start kernels reads: [0, kCntHop1Rows]
+  kCntStartsN = 40,   // k_starts_small: the start list's length
+  kCntStartsE = 41,   // ... and its out-degree sum
+  kCntGlobal = 48,    // [48, 52): counters summed over ranks on the device (dev_allsum's output)
+  kSpecBase = 64,     // the first speculated hop's block
+};
+// a speculated hop's block: kSpecWords words at kSpecBase + kSpecWords * (position in the chain)
+enum SpecWord : int {
+  // [0, kHopWords): the hop's HopWord block
+  kSpecGate = 8,   // its gate (gate_open): 1 the hop ran, 0 it did nothing
+  kSpecRows = 9,   // the DISTINCT _dst output count (a speculated final hop)
+  kSpecSumN = 10,  // several ranks: found / next out-degree sum over ranks of the hop before --
+  kSpecSumE = 11,  // ... published by this hop's gate (piggy) -- or of this hop (dev_allsum)
+  kSpecLastN = 12,  // (piggy) a chain ending on a non-final hop: that hop's sums over ranks
+  kSpecLastE = 13,
+  kSpecWords = 16,
+};
+constexpr int kMaxSpec = (256 - kSpecBase) / kSpecWords;  // hops a chain can hold (12)
+}  // namespace
+
 // the block's sums straight into out[0, k) with no-return atomics (option bu_atomic_sums: the
 // bottom-up passes then need no k_reduce_partials launch; out starts at zero).
 // shards > 1: block b adds into shard b % shards, kShardStride words further per shard, and every
@@ -897,7 +952,8 @@ __device__ inline void bu_rest_scan(const bool (&pend)[R], bool (&found)[R], con
 // one-thread k_gate launch cost ~4.6 us a hop).  e == nullptr: not gated.
 // Several ranks (all != nullptr): the previous hop's (n, e) of every rank arrived with this
 // hop's frontier allgather (all[2r], all[2r + 1]); the gate sums them and block 0 also publishes
-// the sums at gate[2], gate[3] (the host's global counts of the previous hop).
+// the sums at its block's kSpecSumN, kSpecSumE (the host's global counts of the previous hop;
+// `gate` is the block's kSpecGate word).
 struct GateIn {
   const unsigned long long* e = nullptr;
   const unsigned long long* n = nullptr;
@@ -922,8 +978,8 @@ __device__ inline bool gate_open(const GateIn& gi, unsigned long long* gate) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     __hip_atomic_store(gate, open ? 1ull : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (gi.all) {
-      __hip_atomic_store(gate + 2, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(gate + 3, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(gate + (kSpecSumN - kSpecGate), n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(gate + (kSpecSumE - kSpecGate), e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
   return open;
@@ -1803,8 +1859,8 @@ __global__ __launch_bounds__(256) void k_compact(uint8_t* map, int64_t lo, int64
 }
 
 // starts (gidx) -> deduplicated frontier: bitmap bits (set once, by a returning atomicOr) and
-// list of the starts with out-edges; Kd[0] list length, Kd[12] vertices, Kd[13] out-degree sum
-// (the counters launch_compact leaves)
+// list of the starts with out-edges; counts kCntList, kCntSet and kCntDegSum (the counters
+// launch_compact leaves)
 __global__ void k_starts_bits(const int32_t* g, int64_t n, int64_t lo, int64_t hi, const uint32_t* odeg,
                               uint32_t* bits, int32_t* out, unsigned long long* Kd) {
   const int64_t stride = int64_t(gridDim.x) * blockDim.x;
@@ -1823,11 +1879,11 @@ __global__ void k_starts_bits(const int32_t* g, int64_t n, int64_t lo, int64_t h
         keep = od && !(atomicOr(bits + (loc >> 5), bit) & bit);
       }
     }
-    const int64_t s = wave_append(Kd, keep);
+    const int64_t s = wave_append(Kd + kCntList, keep);
     if (keep) {
       out[s] = loc;
-      atomicAdd(Kd + 12, 1ull);
-      atomicAdd(Kd + 13, (unsigned long long)od);
+      atomicAdd(Kd + kCntSet, 1ull);
+      atomicAdd(Kd + kCntDegSum, (unsigned long long)od);
     }
   }
 }
@@ -1839,9 +1895,9 @@ __global__ void k_starts_bits(const int32_t* g, int64_t n, int64_t lo, int64_t h
 // start vids up (gidx -> g), dedup through the start words of the frontier bitmap (only those
 // words are cleared: a top-down first hop never reads the rest, k_compact rewrites it all), keep
 // starts with out-edges (row_ok) as the list F, write its exclusive degree scan to off[0, ns]
-// (entries past the list: degree 0, row 0) and the counts: Kd[40] list length, Kd[41] its
-// out-degree sum, Kd[30] the degree sum over every start with duplicates (hop-1 rows of a
-// query without DISTINCT rescan duplicate starts, QueryBaseProcessor.inl:462-505).
+// (entries past the list: degree 0, row 0) and the counts: kCntStartsN list length, kCntStartsE
+// its out-degree sum, kCntHop1Rows the degree sum over every start with duplicates (hop-1 rows of
+// a query without DISTINCT rescan duplicate starts, QueryBaseProcessor.inl:462-505).
 constexpr int kSmallStarts = 4096;
 __global__ __launch_bounds__(1024) void k_starts_small(const int64_t* __restrict__ vids, int32_t ns, const int64_t* keys,
                                                        const int32_t* vals, uint64_t mask, bool has_min,
@@ -1916,9 +1972,9 @@ __global__ __launch_bounds__(1024) void k_starts_small(const int64_t* __restrict
   if (tid == 0) {
     unsigned long long t = 0;
     for (int w = 0; w < int(blockDim.x >> 6); w++) t += s_w[w];
-    Kd[40] = nF;
-    Kd[41] = E;
-    Kd[30] = t;
+    Kd[kCntStartsN] = nF;
+    Kd[kCntStartsE] = E;
+    Kd[kCntHop1Rows] = t;
   }
   // the hop-1 expansion's tile-row table (k_tile_rows' rule) from the offsets just written: one
   // launch and its gap less before the first hop.  Tile t's row is the last kept start whose
@@ -2010,7 +2066,7 @@ __global__ void k_or_segments_to_map(const uint32_t* recv, int G, int64_t nw, ui
 // several ranks, a top-down hop whose next frontier goes on as a bitmap (bottom-up hops): OR the
 // [G][nw] received mark words straight into the owned frontier bitmap, dropping vertices without
 // out-edges, with the compaction's counts -- sums[0] vertices set, [1] kept out-degree sum,
-// [2] kept vertices (k_compact's Kd[12, 15)) -- instead of writing the marks into the byte map
+// [2] kept vertices (k_compact's [kCntSet, kCntKept]) -- instead of writing the marks into the byte map
 // and compacting it again (k_or_segments_to_map + k_compact: 6 + 29 us at RMAT-26, r12h)
 __global__ __launch_bounds__(256) void k_or_segments_bits(const uint32_t* __restrict__ recv, int G, int64_t nw,
                                                           const uint32_t* __restrict__ odeg, uint32_t* bits,
@@ -2229,9 +2285,20 @@ void exclusive_scan_dev(Ctx& c, const T* in, T* out, int64_t n) {
   NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, in, out, T(0), size_t(n), rocprim::plus<T>(), c.stream));
 }
 
+// rocprim::select in its two calls (size query, run): in[i] with flags[i] != 0 to out, in order;
+// their count to *cnt (device)
+template <typename In, typename Flags, typename Out>
+void select_dev(Ctx& c, In in, Flags flags, Out out, uint64_t* cnt, int64_t n) {
+  size_t tb = 0;
+  NBG_HIP(rocprim::select(nullptr, tb, in, flags, out, cnt, size_t(n), c.stream));
+  c.ws_tmp.ensure(tb);
+  NBG_HIP(rocprim::select(c.ws_tmp.p, tb, in, flags, out, cnt, size_t(n), c.stream));
+}
+
+// a query's counter block (CounterWord / SpecWord index both)
 struct Counters {
   unsigned long long* d;  // device counters
-  unsigned long long* h;  // pinned host mirror (64 entries)
+  unsigned long long* h;  // pinned host mirror (256 entries)
 };
 
 }  // namespace
@@ -2343,14 +2410,12 @@ void ensure_workspaces(Ctx& c, int64_t nF_cap) {
   c.ws_front[0].ensure(size_t(nF_cap + 64) * 4);
   c.ws_front[1].ensure(size_t(nF_cap + 64) * 4);
   c.ws_off.ensure(size_t(nF_cap + 2) * 8);
-  // [0, 64) hop counters, [64, 256) speculative hop blocks; then shards 1 .. kSumShards - 1 of
-  // every word (block_add_sums), kShardStride words apart
-  c.ws_counters.ensure(kShardStride * kSumShards * 8);
+  c.ws_counters.ensure(kShardStride * kSumShards * 8);  // layout: CounterWord / SpecWord
   c.ws_partials.ensure(size_t(kAggBlocks) * kSlots * 8);
   c.ws_bits_send.ensure(size_t(mb / 8 + 64));
   c.ws_bits_recv.ensure(size_t(mb / 8 + 64));
   if (c.sharded) {
-    c.ws_piggy.ensure(size_t(12) * size_t(c.world) * 16 + 64);  // spec hops' counters of every rank
+    c.ws_piggy.ensure(size_t(kMaxSpec) * size_t(c.world) * 16 + 64);  // spec hops' (n, e) of every rank
     c.ws_bits_glob.ensure(size_t(mb / 8 + 64));
     c.ws_bits_xchg.ensure(size_t(c.world) * size_t((c.owned_hi() - c.owned_lo()) / 8) + 64);
   }
@@ -2551,21 +2616,12 @@ int64_t shuffle_rows(Ctx& c, YieldArgs& ya, std::vector<DevBuf>& cols, int64_t n
     if (!all[me * G + p]) continue;
     k_flag_dest<<<grid_cap(n), 256, 0, c.stream>>>(dest.as<uint32_t>(), n, uint32_t(p), flag.as<uint8_t>());
     for (size_t cc = 0; cc < cols.size(); cc++) {
-      size_t tb = 0;
       if (ya.cols[cc].type == VT_BOOL) {
         uint8_t* o = send[cc].as<uint8_t>() + soff[p];
-        NBG_HIP(rocprim::select(nullptr, tb, cols[cc].as<uint8_t>(), flag.as<uint8_t>(), o, cnt.as<uint64_t>(),
-                                size_t(n), c.stream));
-        c.ws_tmp.ensure(tb);
-        NBG_HIP(rocprim::select(c.ws_tmp.p, tb, cols[cc].as<uint8_t>(), flag.as<uint8_t>(), o, cnt.as<uint64_t>(),
-                                size_t(n), c.stream));
+        select_dev(c, cols[cc].as<uint8_t>(), flag.as<uint8_t>(), o, cnt.as<uint64_t>(), n);
       } else {
         int64_t* o = send[cc].as<int64_t>() + soff[p];
-        NBG_HIP(rocprim::select(nullptr, tb, cols[cc].as<int64_t>(), flag.as<uint8_t>(), o, cnt.as<uint64_t>(),
-                                size_t(n), c.stream));
-        c.ws_tmp.ensure(tb);
-        NBG_HIP(rocprim::select(c.ws_tmp.p, tb, cols[cc].as<int64_t>(), flag.as<uint8_t>(), o, cnt.as<uint64_t>(),
-                                size_t(n), c.stream));
+        select_dev(c, cols[cc].as<int64_t>(), flag.as<uint8_t>(), o, cnt.as<uint64_t>(), n);
       }
     }
   }
@@ -2618,17 +2674,17 @@ void launch_compact(Ctx& c, uint8_t* map, int64_t lo, int64_t n, const int64_t* 
                     int require_deg, int32_t* out, uint16_t* bits, unsigned long long* Kd,
                     const uint32_t* odeg = nullptr, bool sums_zero = false, int shards = 1, int64_t own_lo = 0,
                     int64_t own_hi = -1, uint16_t* own_bits = nullptr, int64_t n_read = -1) {
-  // counters: Kd[0] list length (atomic), Kd[12] vertices set, Kd[13] kept out-degree sum,
-  // Kd[14] kept vertices (= the list length, also when out == nullptr writes no list).
-  // sums_zero: Kd[12, 15) are already zero, so the blocks add into them (bu_atomic_sums)
+  // counters (CounterWord): kCntList the list length (atomic) and the sums kCntSet, kCntDegSum,
+  // kCntKept (with own_lo / own_hi also kCntOwnKept, kCntOwnDegSum).
+  // sums_zero: the sums' words are already zero, so the blocks add into them (bu_atomic_sums)
   unsigned long long* partials = c.ws_partials.as<unsigned long long>();
   int64_t ntiles = ((n + 15) / 16 + 1023) / 1024;
   int grid = int(std::max<int64_t>(1, std::min<int64_t>(ntiles, std::min<int64_t>(kAggBlocks, c.opt("compact_grid", 1024)))));
   const bool atomic = sums_zero && c.opt("bu_atomic_sums", 1) != 0;
   k_compact<<<grid, 256, 0, c.stream>>>(map, lo, n, row_ptr, row_ok, require_deg, out, Kd, partials, bits, odeg,
-                                        atomic ? Kd + 12 : nullptr, atomic ? shards : 1, own_lo, own_hi, own_bits,
+                                        atomic ? Kd + kCntSet : nullptr, atomic ? shards : 1, own_lo, own_hi, own_bits,
                                         n_read >= 0 ? n_read : n);
-  if (!atomic) k_reduce_partials<<<1, 1024, 0, c.stream>>>(partials, grid, Kd + 12);
+  if (!atomic) k_reduce_partials<<<1, 1024, 0, c.stream>>>(partials, grid, Kd + kCntSet);
   NBG_HIP(hipGetLastError());
 }
 
@@ -2791,7 +2847,13 @@ FinArgs fin_args(const QArgs& q) {
 // frontier vertex has an in-edge (it was found) and an out-edge (the hops keep only those).
 // Probes past that bound are out of bounds of their buffer resource (the hardware answers 0
 // without a memory access).
-size_t launch_bu_lean(Ctx& c, EdgeSpace& es, const uint32_t* fb, uint32_t* nbits, const uint32_t* odeg, int pk,
+struct BuLaunch {
+  size_t ev_first = kNoEvent;  // timing event at the end of the first pass (the hop's kernel_ms)
+  std::string k0, k1;          // rocprof names of the first-pass and the rest-pass kernel
+  bool rest_rec = false;       // the rest pass read the rest records
+  uint64_t od_bytes = 0;       // out-degree bytes the first pass read (non-final hop)
+};
+BuLaunch launch_bu_lean(Ctx& c, EdgeSpace& es, const uint32_t* fb, uint32_t* nbits, const uint32_t* odeg, int pk,
                       const FastArgs& fp, int fcol, unsigned long long* out, bool hop_front,
                       unsigned long long* gate = nullptr, GateIn gi = GateIn{}, bool out_zero = false,
                       int shards = 1) {
@@ -2969,15 +3031,17 @@ size_t launch_bu_lean(Ctx& c, EdgeSpace& es, const uint32_t* fb, uint32_t* nbits
   else
     snprintf(nm, sizeof nm, "nbg::k_bu_lean<%d, 1, %d, %d%s>", pk, cw > 0 ? 1 : 0, probe_stats ? 1 : 0,
              sel == 8 ? ", 1, 3" : ", 0, 0");
-  c.bu_kernel_name = nm;
+  BuLaunch L;
+  L.ev_first = ev_first;
+  L.k0 = nm;
   // the non-final first pass reads one out-degree per row of its work tiles: 1 B (odeg8, the
   // non-temporal instantiations) or 4 B (odeg)
-  if (!fast) c.bu_od_bytes = uint64_t(work) * 128u * (sel == 8 ? 1u : 4u);
+  if (!fast) L.od_bytes = uint64_t(work) * 128u * (sel == 8 ? 1u : 4u);
   const int wn = fast ? (W == 1 || W == 2 || W == 4 ? W : 8) : 0;
   snprintf(nm, sizeof nm, "nbg::k_bu_rest_lean<%d, %d, %d, %d>", pk, wn, rcw > 0 ? 1 : 0, use_rec ? 1 : 0);
-  c.bu_rest_rec = use_rec;
-  c.bu_rest_name = nm;
-  return ev_first;
+  L.rest_rec = use_rec;
+  L.k1 = nm;
+  return L;
 }
 
 // byte models of a bottom-up hop's two passes from their counters.
@@ -2986,10 +3050,10 @@ size_t launch_bu_lean(Ctx& c, EdgeSpace& es, const uint32_t* fb, uint32_t* nbits
 // rounds 2-4 counted 4 B for every row, 1.5x the bytes the default kernel reads).  Rest pass:
 // a row_ptr pair (or a 64 B rest record) per pending row, 4 B per entry read, predicate values read.
 uint64_t bu_first_bytes(const unsigned long long* h, int64_t n_rows, uint64_t od_bytes) {
-  return h[2] * 4 + 3 * (uint64_t(n_rows) / 8) + od_bytes;
+  return h[kHopSlabWords] * 4 + 3 * (uint64_t(n_rows) / 8) + od_bytes;
 }
 uint64_t bu_rest_bytes(const unsigned long long* h, int pred_width, bool rec) {
-  return h[3] * (rec ? 64 : 16) + h[4] * 4 + h[5] * uint64_t(pred_width);
+  return h[kHopPending] * (rec ? 64 : 16) + h[kHopEntries] * 4 + h[kHopValues] * uint64_t(pred_width);
 }
 // algorithmic bytes of one expansion (DESIGN.md "byte model"): frontier id 4 B + row_ptr pair
 // 16 B + off 8 B per frontier entry; per edge: col 4 B (+ predicate column width) + the
@@ -2998,6 +3062,32 @@ uint64_t expand_bytes(int64_t nF, int64_t E, int pred_width, int mode) {
   uint64_t b = uint64_t(nF) * 28 + uint64_t(E) * (4 + uint64_t(pred_width));
   b += uint64_t(E) * (mode == EXP_ROWS ? 0 : 1);
   return b;
+}
+
+// a lone YIELD _dst (also the default YIELD): no YIELD program runs, the rows are dst vids
+bool is_lone_dst(const std::vector<Program>& yields) {
+  return yields.size() == 1 && yields[0].n == 1 && yields[0].ins[0].op == P_DST;
+}
+// a PK_FAST predicate's typed compare on the CSR's own column (else: no arguments)
+FastArgs fast_args(const Csr& csr, const FastPred& fpk) {
+  if (fpk.kind != PK_FAST) return FastArgs{};
+  const PropCol& pc = csr.props[size_t(fpk.col)];
+  return FastArgs{pc.data.p, pc.present.as<uint8_t>(), pc.width, fpk.op, fpk.k};
+}
+// the predicate can run bottom-up: only when it cannot error (the reference fails the query on
+// any row's eval error, so every row must be evaluated when errors are possible) -- none, or a
+// typed compare on a column without absent values that the transposed CSR carries
+bool pred_runs_bottom_up(const FastPred& fpk, const FastArgs& fp, const EdgeSpace& es) {
+  return fpk.kind == PK_NONE || (fpk.kind == PK_FAST && fp.present == nullptr &&
+                                 es.tr.props.size() > size_t(fpk.col) && es.tr.props[size_t(fpk.col)].data.p);
+}
+// the NBG_T_* column type of a program's VT_* result
+int32_t result_type(int32_t vt) {
+  return vt == VT_DOUBLE ? NBG_T_DOUBLE : vt == VT_BOOL ? NBG_T_BOOL : vt == VT_STR ? NBG_T_STRING : NBG_T_VID;
+}
+// the type a stored column is returned as: FLOAT widens to DOUBLE, VID and TIMESTAMP are INTs
+int32_t column_result_type(int32_t t) {
+  return t == NBG_T_FLOAT ? NBG_T_DOUBLE : (t == NBG_T_VID || t == NBG_T_TIMESTAMP) ? NBG_T_INT : t;
 }
 
 }  // namespace
@@ -3059,237 +3149,91 @@ void global_degree_stats(Ctx& c, EdgeSpace& es) {
 // ------------------------------------------------------------------------------------------
 // GO N STEPS
 // ------------------------------------------------------------------------------------------
-int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
-  PoolScope pool_scope(query_pool(c));
-  if (!c.finalized) throw Error(NBG_E_STATE, "snapshot not finalized");
-  if (s.steps < 1) throw Error(NBG_E_INVALID_ARG, "steps must be >= 1");
-  if (s.edge_type <= 0) throw Error(NBG_E_INVALID_ARG, "GO ... REVERSELY is not supported (GoExecutor.cpp:203-205)");
-  auto it = c.edges.find(s.edge_type);
-  if (it == c.edges.end()) throw Error(NBG_E_INVALID_ARG, "edge type not in snapshot");
-  EdgeSpace& es = it->second;
-  Csr& csr = es.out;
-  c.timing = Timing{};
-  timing_reset(c);
-  // per-hop event pairs (hop stats); bench.py's timed loop turns them off like a production
-  // caller would, its statistics loop on
-  c.hop_timing = c.opt("hop_timing", 1) != 0;
-  if (c.host_stage_used) host_sync(c);  // a failed query's copies
-  c.host_stage_used = 0;
-  c.total_pending = false;
+namespace {
+
+// One GO query: its compiled programs, counter block, frontier and speculation state, and the
+// phases go_run calls in order.
+struct GoQuery {
+  Ctx& c;
+  const nbg_go_spec& s;
+  EdgeSpace& es;
+  Csr& csr;
+  nbg_rows* out;
   // the query's device-time events too are instrumentation: with hop_timing off none is recorded
   // (an event between two launches leaves ~5.5 us between them on the device)
-  const bool tot_ev = c.hop_timing;
-  if (tot_ev) hipEventRecord(c.ev[0], c.stream);
+  const bool tot_ev;
 
-  // compile WHERE / YIELD (errors are deferred to the final step, as the reference only
-  // reports them when the final getNeighbors request is actually sent)
+  // ---- compile() ----
   Program where{};
-  bool has_where = s.where_len > 0;
-  std::string msg;
-  // $- / $var input table columns (validated here, uploaded once the starts are resolved)
-  std::vector<Field> in_fields;
-  if (s.n_inputs) {
-    if (!s.input_names || !s.input_types || !s.input_cols) throw Error(NBG_E_INVALID_ARG, "input table");
-    for (size_t i = 0; i < s.n_inputs; i++) {
-      const int32_t t = s.input_types[i];
-      if (t != NBG_T_VID && t != NBG_T_INT && t != NBG_T_DOUBLE && t != NBG_T_BOOL && t != NBG_T_STRING)
-        throw Error(NBG_E_UNSUPPORTED, "input column type");
-      if (t == NBG_T_STRING && (!s.input_str_offsets || !s.input_str_offsets[i]))
-        throw Error(NBG_E_INVALID_ARG, "input STRING column without offsets");
-      in_fields.push_back(Field{s.input_names[i] ? s.input_names[i] : "", t});
-    }
-  }
+  std::vector<Program> yields;
+  std::vector<Field> in_fields;  // $- / $var input table columns
+  const bool has_where, default_yield;
+  // compile errors are deferred to the final step, as the reference only reports them when the
+  // final getNeighbors request is actually sent
   int32_t deferred = NBG_OK;
   std::string deferred_msg;
-  if (has_where) {
-    int32_t rc = compile_expr(s.where, s.where_len, es.fields, true, true, &where, &msg, &c.tag_refs, in_fields.empty() ? nullptr : &in_fields);
-    if (rc == NBG_E_UNSUPPORTED || rc == NBG_E_INVALID_ARG) throw Error(rc, "WHERE: " + msg);
-    if (rc != NBG_OK) {
-      deferred = rc;
-      deferred_msg = "WHERE: " + msg;
-    }
-  }
-  std::vector<Program> yields;
-  bool default_yield = s.n_yields == 0;
-  if (default_yield) {
-    yields.push_back(program_dst());
-  } else {
-    if (s.n_yields > size_t(kMaxYields)) throw Error(NBG_E_UNSUPPORTED, "too many YIELD columns");
-    for (size_t i = 0; i < s.n_yields; i++) {
-      Program p{};
-      int32_t rc = compile_expr(s.yields[i], s.yield_lens[i], es.fields, true, true, &p, &msg, &c.tag_refs, in_fields.empty() ? nullptr : &in_fields);
-      if (rc == NBG_E_UNSUPPORTED || rc == NBG_E_INVALID_ARG) throw Error(rc, "YIELD: " + msg);
-      if (rc != NBG_OK && deferred == NBG_OK) {
-        deferred = rc;
-        deferred_msg = "YIELD: " + msg;
-      }
-      if (rc == NBG_OK && p.result_type == VT_STR && s.distinct && c.sharded)
-        throw Error(NBG_E_UNSUPPORTED, "DISTINCT over STRING YIELD columns across ranks");
-      yields.push_back(p);
-    }
-  }
-  bool uses_input = false;
-  for (int i = 0; i < where.n && has_where; i++) uses_input |= where.ins[i].op == P_INPUT;
-  for (auto& p : yields)
-    for (int i = 0; i < p.n; i++) uses_input |= p.ins[i].op == P_INPUT;
-  const int64_t lo = c.owned_lo(), hi = c.owned_hi();
-  const int64_t n_own = hi - lo;
-  ensure_workspaces(c, std::max<int64_t>({n_own, int64_t(s.n_starts), 1}));
-  Counters K{c.ws_counters.as<unsigned long long>(), c.host_counters};
-  DevBuf degbuf;
-  uint8_t* map = c.ws_map.as<uint8_t>();
-  uint16_t* bits16 = c.ws_bits_send.as<uint16_t>();  // frontier bitmap written by k_compact
-  const int64_t* row_ptr = csr.row_ptr.as<int64_t>();
-  const bool bu_ok = es.has_tr && c.opt("bottom_up", 1) != 0;
-  const int64_t bu_div = std::max<int64_t>(1, c.opt("bu_div", 4));  // bottom-up when E >= nnz / bu_div
-  const int64_t bu_force = c.opt("bu_force", 0);                     // 1: always, -1: never
-  const uint8_t* row_ok = csr.row_ok.as<uint8_t>();  // rows whose keys sit outside hash(vid)'s part
+  bool uses_input = false, lone_dst = false;  // lone_dst: is_lone_dst(yields)
+  // the WHERE's class and its typed compare, classified once (no deferred error): read by the
+  // speculated final hop and by the final step
+  FastPred fpk{};
+  FastArgs fp{};
+  bool pred_bu = false;    // pred_runs_bottom_up
+  const FastArgs no_fp{};  // the non-final hops evaluate no predicate
 
-  // starts -> gidx
-  int64_t ns = int64_t(s.n_starts);
-  c.ws_starts.ensure(size_t(std::max<int64_t>(ns, 1)) * 12 + 64);
-  int64_t* d_starts = c.ws_starts.as<int64_t>();
-  int32_t* d_sg = reinterpret_cast<int32_t*>(d_starts + std::max<int64_t>(ns, 1));
+  // ---- resolve_starts() ----
+  int64_t lo = 0, hi = 0, n_own = 0, ns = 0;
+  Counters K{};
+  DevBuf degbuf;
+  uint8_t* map = nullptr;
+  const int64_t* row_ptr = nullptr;
+  const uint8_t* row_ok = nullptr;  // rows whose keys sit outside hash(vid)'s part
+  bool bu_ok = false;
+  int64_t bu_div = 4, bu_force = 0;  // bottom-up when E >= nnz / bu_div; force 1: always, -1: never
+  int32_t* d_sg = nullptr;           // the starts' gidx
   // a first hop that is certainly top-down (no transposed CSR, or even the ns largest
-  // out-degrees sum below the bottom-up threshold) from a few starts on one rank: one launch
-  // builds its frontier and degree scan (k_starts_small) and the hop runs without a round trip
-  // (the expansion reads the frontier size from the scan; the counts come back with the
-  // compaction's)
-  if (es.out_nnz_global < 0) global_degree_stats(c, es);
-  // a first hop from ns starts is certainly top-down when even the ns largest out-degrees sum
-  // below the bottom-up threshold
-  const int64_t deg_bound = ns < int64_t(es.top_deg.size()) ? es.top_deg[size_t(ns)]
-                            : es.max_odeg_global >= 0       ? ns * es.max_odeg_global
-                                                            : INT64_MAX;
-  const bool td1_certain =
-      !bu_ok || bu_force < 0 || (bu_force == 0 && deg_bound < es.out_nnz_global / bu_div);
+  // out-degrees sum below the bottom-up threshold) from a few starts: one launch builds its
+  // frontier and degree scan (k_starts_small) and the hop runs without a round trip (the
+  // expansion reads the frontier size from the scan; the counts come back with the compaction's)
   // (with several ranks each rank's k_starts_small keeps its own starts; the hop-1 marks are
   // exchanged before the compaction)
-  const bool fast1 = ns > 0 && ns <= kSmallStarts && s.steps >= 2 && td1_certain && !(uses_input && s.steps > 1) &&
-                     c.opt("starts_small", 1) != 0;
-  // counters summed over ranks on the device (dev_allsum) land at K.d[48, 52)
-  const bool multi = c.sharded;
-  // one rank: the hop-1 compaction and the speculated hops add their block sums into kSumShards
-  // shards (option sum_shards; block_add_sums), folded by their readers -- the gates and the
-  // counter fetches below.  Shards are zero at the query start (k_starts_small / the memset);
-  // clean_shards zeroes them again before any later dense use of the same words.
-  const int ks = multi ? 1 : int(std::min<int64_t>(std::max<int64_t>(c.opt("sum_shards", kSumShards), 1), kSumShards));
-  bool shards_dirty = false;
-  auto clean_shards = [&]() {
-    if (!shards_dirty) return;
-    NBG_HIP(hipMemsetAsync(K.d + kShardStride, 0, kShardStride * size_t(ks - 1) * 8, c.stream));
-    shards_dirty = false;
-  };
-  // the small-start path's one block reads the starts from coherent pinned host memory (the
-  // stream's previous query finished before this one was enqueued): no copy between queries
-  const int64_t* k_starts = d_starts;
-  if (ns && fast1 && c.starts_host) {
-    memcpy(c.starts_host, s.starts, size_t(ns) * 8);
-    k_starts = c.starts_host;
-  } else if (ns) {
-    c.h2d(d_starts, s.starts, size_t(ns) * 8);
-    if (!fast1) lookup_gidx(c, d_starts, d_sg, ns);
-  }
-  int cur = 0;
-  int64_t E_known = -1;  // frontier out-degree sum when a compaction already produced it
-  int32_t* F = c.ws_front[0].as<int32_t>();
-  int64_t nF = 0;
-  int64_t nset_global = ns;  // "starts_ non-empty" (GoExecutor.cpp:93-97)
-  int64_t hop1_scanned = -1;  // hop-1 rows with duplicate starts rescanned (k_starts_degree)
-  int64_t Eg_known = -1;      // several ranks: the start frontier's out-degree sum over ranks
+  bool fast1 = false;
+  bool multi = false;  // counters summed over ranks on the device (dev_allsum) land at kCntGlobal
   // several ranks (option go_rep1): every rank runs the whole first hop -- every start, over a
   // replica of the out CSR (ensure_rep_out, built on first use) -- into a frontier bitmap over the
   // whole gidx space, so the hop needs no mark exchange and the second hop no frontier allgather:
   // one collective a C3 query instead of three.  (The same branch on every rank: ns, the degree
   // statistics and the options are the same everywhere.)
+  bool rep1 = false;
+  const Csr* csr1 = nullptr;  // the first hop's rows (rep1: the replica)
+  int64_t max_odeg1 = -1;
   // the marks of a top-down hop over this edge type are its dsts: rows with an in-edge, the
   // first bu_in_tiles tiles of the owned range (class-ordered numbering); the compactions read
   // the byte map that far and write the bitmap past it as zero
-  const int64_t map_bound = es.has_tr && es.bu_in_tiles > 0 ? std::min<int64_t>(n_own, es.bu_in_tiles * 128) : n_own;
-  const bool rep1 = fast1 && multi && bu_ok && c.opt("compact_list", 0) == 0 && es.odeg.p && c.opt("go_rep1", 1) != 0;
-  const Csr& csr1 = rep1 ? es.rep_out : csr;  // the first hop's rows
-  if (rep1) {
-    ensure_rep_out(c, es);
-    c.ws_bits_rep1.ensure(size_t(map_bytes(c) / 8 + 64));
-  }
-  // the hop-1 expansion's tile-row table is written by k_starts_small (sized for the degree bound)
-  const bool starts_tiles = fast1;
-  const int64_t max_odeg1 = rep1 ? es.max_odeg_global : es.max_odeg;
-  if (starts_tiles) {
-    const int64_t eb = std::max<int64_t>(1, max_odeg1 >= 0 ? int64_t(ns) * max_odeg1 : csr1.nnz);
-    c.ws_tile_rows.ensure(size_t(std::min<int64_t>(eb, csr1.nnz + 1) / kTile + 4) * 4);
-  }
-  if (fast1) {
-    k_starts_small<<<1, 1024, 0, c.stream>>>(
-        k_starts, int32_t(ns), c.ht_keys.as<int64_t>(), c.ht_vals.as<int32_t>(), uint64_t(c.ht_cap - 1), c.ht_has_min,
-        c.ht_min_gidx, d_sg, rep1 ? 0 : lo, rep1 ? c.n_global : hi, csr1.row_ptr.as<int64_t>(),
-        csr1.row_ok.as<uint8_t>(), rep1 ? c.ws_bits_rep1.as<uint32_t>() : reinterpret_cast<uint32_t*>(bits16), F,
-        c.ws_off.as<int64_t>(), K.d, starts_tiles ? c.ws_tile_rows.as<int32_t>() : nullptr);
-    NBG_HIP(hipGetLastError());
-    nF = ns;  // an upper bound: the entries past the list have degree 0
-  } else {
-    NBG_HIP(hipMemsetAsync(K.d, 0, kShardStride * kSumShards * 8, c.stream));
-  }
-  if (ns && !fast1) {
-    if (s.steps == 1 && !s.distinct) {
-      k_list_starts<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, row_ptr, row_ok, F, K.d);
-    } else if (!c.sharded && es.odeg.p) {
-      // one rank: dedup the starts through the frontier bitmap itself (a few hundred atomics)
-      // instead of marking the byte map and compacting the whole vertex space
-      NBG_HIP(hipMemsetAsync(bits16, 0, c.ws_bits_send.bytes, c.stream));
-      k_starts_bits<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, es.odeg.as<uint32_t>(),
-                                                        reinterpret_cast<uint32_t*>(bits16), F, K.d);
-      if (!s.distinct)
-        k_starts_degree<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, row_ptr, row_ok, K.d + 30);
-    } else {
-      k_mark_gidx<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, map);
-      launch_compact(c, map, lo, n_own, row_ptr, row_ok, 1, F, bits16, K.d, es.odeg.as<uint32_t>());
-      if (!s.distinct)
-        k_starts_degree<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, row_ptr, row_ok, K.d + 30);
-    }
-    NBG_HIP(hipGetLastError());
-    const bool counted = !(s.steps == 1 && !s.distinct);
-    if (multi && counted) dev_allsum(c, K.d, {13}, K.d + 48);
-    fetch_counters(c, K.d, multi && counted ? 52 : 32, K.h);
-    nF = int64_t(K.h[0]);
-    if (counted) {
-      E_known = int64_t(K.h[13]);
-      if (multi) Eg_known = int64_t(K.h[48]);
-      if (!s.distinct) hop1_scanned = int64_t(K.h[30]);
-    }
-  }
-  unsigned long long* red = K.d + 24;  // scratch of the cross-rank sums
-  auto finish_empty = [&]() -> int32_t {
-    auto* h = new HostRows();
-    for (auto& p : yields) {
-      h->types.push_back(p.result_type == VT_DOUBLE ? NBG_T_DOUBLE
-                         : p.result_type == VT_BOOL ? NBG_T_BOOL
-                         : p.result_type == VT_STR  ? NBG_T_STRING
-                                                    : NBG_T_VID);
-      h->cols.push_back(nullptr);
-      h->str_off.push_back(nullptr);
-    }
-    fill_rows(out, h, 0, s.keep_on_device != 0);
-    hipEventRecord(c.ev[1], c.stream);
-    hipEventSynchronize(c.ev[1]);
-    float ms = 0;
-    hipEventElapsedTime(&ms, c.ev[0], c.ev[1]);
-    c.timing.total_ms = ms;
-    out->edges_scanned = c.timing.edges_scanned;
-    return NBG_OK;
-  };
-  if (nset_global == 0) return finish_empty();
+  int64_t map_bound = 0;
+  int64_t hop1_scanned = -1;  // hop-1 rows with duplicate starts rescanned (k_starts_degree)
+  int64_t Eg_known = -1;      // several ranks: the start frontier's out-degree sum over ranks
+  // one rank: the hop-1 compaction and the speculated hops add their block sums into kSumShards
+  // shards (option sum_shards; block_add_sums), folded by their readers -- the gates and the
+  // counter fetches.  Shards are zero at the query start (k_starts_small / the memset);
+  // clean_shards zeroes them again before any later dense use of the same words.
+  int ks = 1;
+  bool shards_dirty = false;
 
+  // ---- frontier state: a list of local rows (top-down) and/or a bitmap (bottom-up) ----
+  int32_t* F = nullptr;
+  int64_t nF = 0;
+  int cur = 0;
+  bool have_list = true, off_ready = false;
+  // E = sum of the frontier's out-degrees = the adjacency entries the hop scans (TEPS numerator,
+  // SURVEY 8d); E_known: when a compaction already produced it; Eg: over all ranks
+  int64_t E = -1, E_known = -1, Eg = 0;
+  int64_t list_n = -1;      // length of the list the bitmap will compact to, when already counted
+  int64_t nset_global = 0;  // "starts_ non-empty" (GoExecutor.cpp:93-97)
+  uint32_t *bitsA = nullptr, *bitsB = nullptr;  // the frontier bitmap (k_compact / bottom-up hops) and the next
+
+  // ---- bind_inputs() ----
   ExpandArgs a{};
-  a.row_ptr = row_ptr;
-  a.col = csr.col.as<int32_t>();
-  a.lo = lo;
-  a.map = map;
-  a.err = K.d + 4;
-  a.storage = 0;
-  a.mark_check = 0;
-  FastArgs fp{};
-  EvalEnv env = make_env(c, es, csr, s.edge_type);
+  EvalEnv env{};
   DevBuf in_keys, in_rows, in_tab;
   std::vector<DevBuf> in_cols;
   // STEPS > 1: graphd maps every dst of a non-final step back to a start (VertexBackTracker,
@@ -3297,131 +3241,350 @@ int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
   // order-dependent whenever a vertex is reached from several starts.  The build's rule
   // (DESIGN.md): each hop reads the previous hop's roots and a dst takes the smallest root vid
   // among its in-edges' srcs; it is the reference's answer whenever the root is unique.
-  const bool multi_root = uses_input && s.steps > 1;
+  bool multi_root = false;
   DevBuf root_buf[2], root_tab;
   int root_cur = 0;
-  if (multi_root) {
-    // rank of every start's vid among the distinct start vids
-    std::vector<int64_t> u(s.starts, s.starts + ns);
-    std::sort(u.begin(), u.end());
-    u.erase(std::unique(u.begin(), u.end()), u.end());
-    std::vector<int32_t> rk(size_t(std::max<int64_t>(ns, 1)));
-    for (int64_t i = 0; i < ns; i++)
-      rk[size_t(i)] = int32_t(std::lower_bound(u.begin(), u.end(), s.starts[i]) - u.begin());
-    DevBuf drk;
-    drk.alloc(rk.size() * 4);
-    NBG_HIP(hipMemcpyAsync(drk.p, rk.data(), rk.size() * 4, hipMemcpyHostToDevice, c.stream));
-    for (auto& b : root_buf) {
-      b.alloc(size_t(c.n_global + 1) * 4);
-      NBG_HIP(hipMemsetAsync(b.p, 0x7f, size_t(c.n_global + 1) * 4, c.stream));  // > every rank
-    }
-    root_tab.alloc(std::max<size_t>(u.size(), 1) * 4);
-    if (ns) k_root_init<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, drk.as<int32_t>(), ns, root_buf[0].as<int32_t>(),
-                                                           root_tab.as<int32_t>());
-    host_sync(c);  // rk is pageable host memory
-  }
-  if (uses_input) {
-    uint32_t cap = 64;
-    while (cap < uint32_t(2 * std::max<int64_t>(ns, 1))) cap <<= 1;
-    in_keys.alloc(size_t(cap) * 4);
-    in_rows.alloc(size_t(cap) * 4);
-    NBG_HIP(hipMemsetAsync(in_keys.p, 0xff, size_t(cap) * 4, c.stream));
-    NBG_HIP(hipMemsetAsync(in_rows.p, 0xff, size_t(cap) * 4, c.stream));
-    if (ns) k_input_index<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, in_keys.as<int32_t>(), in_rows.as<int32_t>(), cap - 1);
-    NBG_HIP(hipGetLastError());
-    std::vector<PropDev> tab;
-    for (size_t i = 0; i < s.n_inputs; i++) {
-      const int32_t t = s.input_types[i];
-      const size_t w = t == NBG_T_BOOL ? 1 : 8;
-      DevBuf col, off;
-      PropDev pd{t, int32_t(w), nullptr, nullptr, nullptr, nullptr};
-      if (t != NBG_T_STRING) {
-        col.alloc(std::max<size_t>(size_t(ns) * w, 8));
-        if (ns) NBG_HIP(hipMemcpyAsync(col.p, s.input_cols[i], size_t(ns) * w, hipMemcpyHostToDevice, c.stream));
-        pd.data = col.p;
-      } else {
-        const int64_t* ho = s.input_str_offsets[i];
-        off.alloc(size_t(ns + 1) * 8);
-        NBG_HIP(hipMemcpyAsync(off.p, ho, size_t(ns + 1) * 8, hipMemcpyHostToDevice, c.stream));
-        col.alloc(size_t(ho[ns]) + 8);
-        if (ho[ns]) NBG_HIP(hipMemcpyAsync(col.p, s.input_cols[i], size_t(ho[ns]), hipMemcpyHostToDevice, c.stream));
-        pd = PropDev{t, 8, nullptr, nullptr, off.as<int64_t>(), col.as<uint8_t>()};
-      }
-      tab.push_back(pd);
-      in_cols.push_back(std::move(col));
-      in_cols.push_back(std::move(off));
-    }
-    in_tab.alloc(sizeof(PropDev) * tab.size());
-    NBG_HIP(hipMemcpyAsync(in_tab.p, tab.data(), sizeof(PropDev) * tab.size(), hipMemcpyHostToDevice, c.stream));
-    host_sync(c);  // `tab` is pageable host memory
-    env.in_keys = in_keys.as<int32_t>();
-    env.in_rows = in_rows.as<int32_t>();
-    env.in_mask = cap - 1;
-    env.iprops = in_tab.as<PropDev>();
-  }
 
-  // Frontier state: a list of local rows (top-down) and/or a bitmap (bottom-up).  E = sum of
-  // the frontier's out-degrees = the adjacency entries the hop scans (TEPS numerator).
-  uint32_t* bitsA = c.ws_bits_send.as<uint32_t>();
-  uint32_t* bitsB = c.ws_bits_recv.as<uint32_t>();
-  bool have_list = true, off_ready = false;
-  int64_t E = -1;
-  int64_t list_n = -1;  // length of the list the bitmap will compact to, when already counted
-  auto ensure_list = [&]() {
-    if (have_list) return;
-    cur ^= 1;
-    F = c.ws_front[cur].as<int32_t>();
-    NBG_HIP(hipMemsetAsync(K.d, 0, 8, c.stream));
-    k_bits_compact<0><<<grid_cap((n_own + 31) / 32, 1024, 4096), 1024, 0, c.stream>>>(bitsA, n_own, lo, nullptr, F,
-                                                                                     K.d);
-    if (list_n >= 0) {
-      nF = list_n;  // counted by the compaction that wrote the bitmap: no round trip
-    } else {
-      fetch_counters(c, K.d, 1, K.h);
-      nF = int64_t(K.h[0]);
-    }
-    list_n = -1;
-    have_list = true;
-    off_ready = false;
-  };
-  auto ensure_off = [&]() {
-    ensure_list();
-    if (!off_ready) {
-      int64_t e2 = nF ? degree_scan(c, F, nF, csr, degbuf, E_known) : 0;
-      E = e2;
-      E_known = e2;
-      off_ready = true;
-    }
-  };
-  // direction choice is global (every rank must take the same branch: bottom-up allgathers)
-  auto want_bu = [&](int64_t eg) {  // (multi-step roots need every in-edge: top-down only)
-    return eg > 0 && bu_ok && !multi_root && bu_force >= 0 && (bu_force > 0 || eg >= es.out_nnz_global / bu_div);
-  };
-  int64_t Eg = 0;  // frontier out-degree sum over all ranks
-  // Speculative bottom-up hops (one rank).  A direction choice needs the previous hop's counters
-  // on the host, one round trip per hop; instead, right after a top-down hop's compaction, the
+  // ---- the speculation chain ----
+  // Speculative bottom-up hops.  A direction choice needs the previous hop's counters on the
+  // host, one round trip per hop; instead, right after a top-down hop's compaction, the
   // remaining hops are enqueued as bottom-up hops gated on the device (GateIn: the same rule as
   // want_bu, on the same counters) before the one counter fetch.  A hop whose gate is 0 does
   // nothing (every kernel returns at once), and the host continues from there as before: the
   // direction never changes a hop's result, only its cost.  The final step is speculated only
   // as the DISTINCT _dst bottom-up hop (a predicate that cannot error, no deferred compile
-  // error).  Blocks of 16 words from K.d[64]: [0, 8) the hop's counters, [8] its gate, [9] the
-  // DISTINCT output count, [10, 12) found / next out-degree sum over ranks (several ranks).
+  // error).  Each hop has a SpecWord block in the counters.
+  // (several ranks: each gate reads counters summed over ranks on the device, dev_allsum, and
+  // every rank enqueues the same chain of collectives, so every rank takes the same branches)
   struct Spec {
     int32_t hop;  // Timing::hops index it will take
     bool final;
-    std::string k0, k1;
+    BuLaunch L;  // what its own launch ran
   };
   std::vector<Spec> spec;
-  DevBuf spec_vids;
+  bool spec_ok = false, fin_spec = false;  // hops / the final step can be speculated
+  unsigned long long spec_thr = 1;
+  bool spec_blocks_used = false;
+  // several ranks (piggy): every speculated hop's frontier allgather carries the previous hop's
+  // (n, e) of every rank to its gate (GateIn::all), one exchange per hop instead of an allgather
+  // and an all-reduce
+  bool piggy_used = false;
   // option host_direct: a DISTINCT _dst result that goes to the host is written by the bottom-up
   // output kernel straight into pinned host memory (mapped into the device's address space), so
   // the hand-out copies nothing
   // (r06j: stores from the device reach 54.6 GB/s into pinned host memory, hipMemcpyAsync 29.7:
   // C3's 173 MB hand-out 7.4 -> 3.8 ms end to end)
-  const bool host_direct = !s.keep_on_device && c.opt("host_direct", 1) != 0;
+  bool host_direct = false;
+  DevBuf spec_vids;
   HostBuf spec_hvids;
-  auto vid_block = [&](DevBuf& d, HostBuf& hb) -> void* {
+  // the speculated final hop that ran (spec_replay): its block and launch
+  unsigned long long fin_h[kSpecWords] = {};
+  BuLaunch fin_L;
+  bool fin_done = false;
+
+  // ---- the final step ----
+  DevBuf dprog;  // the WHERE program, then the YIELD programs
+  std::unique_ptr<HostRows> rows;
+  int64_t nrows = 0;
+  std::vector<DevBuf> slen;          // STRING yield columns: byte length per row
+  std::map<size_t, bool> host_cols;  // columns already in pinned host memory (host_direct)
+
+  GoQuery(Ctx& c_, const nbg_go_spec& s_, EdgeSpace& es_, nbg_rows* out_)
+      : c(c_), s(s_), es(es_), csr(es_.out), out(out_), tot_ev(c_.hop_timing), has_where(s_.where_len > 0),
+        default_yield(s_.n_yields == 0) {}
+
+  // WHERE / YIELD programs, the input table's columns (validated here, uploaded once the starts
+  // are resolved) and the predicate's class
+  void compile() {
+    std::string msg;
+    if (s.n_inputs) {
+      if (!s.input_names || !s.input_types || !s.input_cols) throw Error(NBG_E_INVALID_ARG, "input table");
+      for (size_t i = 0; i < s.n_inputs; i++) {
+        const int32_t t = s.input_types[i];
+        if (t != NBG_T_VID && t != NBG_T_INT && t != NBG_T_DOUBLE && t != NBG_T_BOOL && t != NBG_T_STRING)
+          throw Error(NBG_E_UNSUPPORTED, "input column type");
+        if (t == NBG_T_STRING && (!s.input_str_offsets || !s.input_str_offsets[i]))
+          throw Error(NBG_E_INVALID_ARG, "input STRING column without offsets");
+        in_fields.push_back(Field{s.input_names[i] ? s.input_names[i] : "", t});
+      }
+    }
+    const std::vector<Field>* inf = in_fields.empty() ? nullptr : &in_fields;
+    if (has_where) {
+      int32_t rc = compile_expr(s.where, s.where_len, es.fields, true, true, &where, &msg, &c.tag_refs, inf);
+      if (rc == NBG_E_UNSUPPORTED || rc == NBG_E_INVALID_ARG) throw Error(rc, "WHERE: " + msg);
+      if (rc != NBG_OK) {
+        deferred = rc;
+        deferred_msg = "WHERE: " + msg;
+      }
+    }
+    if (default_yield) {
+      yields.push_back(program_dst());
+    } else {
+      if (s.n_yields > size_t(kMaxYields)) throw Error(NBG_E_UNSUPPORTED, "too many YIELD columns");
+      for (size_t i = 0; i < s.n_yields; i++) {
+        Program p{};
+        int32_t rc = compile_expr(s.yields[i], s.yield_lens[i], es.fields, true, true, &p, &msg, &c.tag_refs, inf);
+        if (rc == NBG_E_UNSUPPORTED || rc == NBG_E_INVALID_ARG) throw Error(rc, "YIELD: " + msg);
+        if (rc != NBG_OK && deferred == NBG_OK) {
+          deferred = rc;
+          deferred_msg = "YIELD: " + msg;
+        }
+        if (rc == NBG_OK && p.result_type == VT_STR && s.distinct && c.sharded)
+          throw Error(NBG_E_UNSUPPORTED, "DISTINCT over STRING YIELD columns across ranks");
+        yields.push_back(p);
+      }
+    }
+    for (int i = 0; i < where.n && has_where; i++) uses_input |= where.ins[i].op == P_INPUT;
+    for (auto& p : yields)
+      for (int i = 0; i < p.n; i++) uses_input |= p.ins[i].op == P_INPUT;
+    lone_dst = is_lone_dst(yields);
+    if (deferred == NBG_OK) {
+      fpk = has_where ? classify_pred(where, es.fields) : FastPred{};
+      fp = fast_args(csr, fpk);
+      pred_bu = pred_runs_bottom_up(fpk, fp, es);
+      fin_spec = s.distinct && lone_dst && pred_bu;
+    }
+  }
+
+  void clean_shards() {
+    if (!shards_dirty) return;
+    NBG_HIP(hipMemsetAsync(K.d + kShardStride, 0, kShardStride * size_t(ks - 1) * 8, c.stream));
+    shards_dirty = false;
+  }
+
+  // starts -> gidx -> the start frontier: the fast1 and rep1 decisions, then k_starts_small, or
+  // the list / bitmap / byte-map paths with their counter fetch
+  void resolve_starts() {
+    lo = c.owned_lo(), hi = c.owned_hi();
+    n_own = hi - lo;
+    ensure_workspaces(c, std::max<int64_t>({n_own, int64_t(s.n_starts), 1}));
+    K = Counters{c.ws_counters.as<unsigned long long>(), c.host_counters};
+    map = c.ws_map.as<uint8_t>();
+    bitsA = c.ws_bits_send.as<uint32_t>();
+    bitsB = c.ws_bits_recv.as<uint32_t>();
+    uint16_t* bits16 = c.ws_bits_send.as<uint16_t>();  // frontier bitmap written by k_compact
+    row_ptr = csr.row_ptr.as<int64_t>();
+    bu_ok = es.has_tr && c.opt("bottom_up", 1) != 0;
+    bu_div = std::max<int64_t>(1, c.opt("bu_div", 4));
+    bu_force = c.opt("bu_force", 0);
+    row_ok = csr.row_ok.as<uint8_t>();
+    ns = int64_t(s.n_starts);
+    c.ws_starts.ensure(size_t(std::max<int64_t>(ns, 1)) * 12 + 64);
+    int64_t* d_starts = c.ws_starts.as<int64_t>();
+    d_sg = reinterpret_cast<int32_t*>(d_starts + std::max<int64_t>(ns, 1));
+    if (es.out_nnz_global < 0) global_degree_stats(c, es);
+    // a first hop from ns starts is certainly top-down when even the ns largest out-degrees sum
+    // below the bottom-up threshold
+    const int64_t deg_bound = ns < int64_t(es.top_deg.size()) ? es.top_deg[size_t(ns)]
+                              : es.max_odeg_global >= 0       ? ns * es.max_odeg_global
+                                                              : INT64_MAX;
+    const bool td1_certain =
+        !bu_ok || bu_force < 0 || (bu_force == 0 && deg_bound < es.out_nnz_global / bu_div);
+    fast1 = ns > 0 && ns <= kSmallStarts && s.steps >= 2 && td1_certain && !(uses_input && s.steps > 1) &&
+            c.opt("starts_small", 1) != 0;
+    multi = c.sharded;
+    ks = multi ? 1 : int(std::min<int64_t>(std::max<int64_t>(c.opt("sum_shards", kSumShards), 1), kSumShards));
+    // the small-start path's one block reads the starts from coherent pinned host memory (the
+    // stream's previous query finished before this one was enqueued): no copy between queries
+    const int64_t* k_starts = d_starts;
+    if (ns && fast1 && c.starts_host) {
+      memcpy(c.starts_host, s.starts, size_t(ns) * 8);
+      k_starts = c.starts_host;
+    } else if (ns) {
+      c.h2d(d_starts, s.starts, size_t(ns) * 8);
+      if (!fast1) lookup_gidx(c, d_starts, d_sg, ns);
+    }
+    F = c.ws_front[0].as<int32_t>();
+    nset_global = ns;
+    map_bound = es.has_tr && es.bu_in_tiles > 0 ? std::min<int64_t>(n_own, es.bu_in_tiles * 128) : n_own;
+    rep1 = fast1 && multi && bu_ok && c.opt("compact_list", 0) == 0 && es.odeg.p && c.opt("go_rep1", 1) != 0;
+    csr1 = rep1 ? &es.rep_out : &csr;
+    if (rep1) {
+      ensure_rep_out(c, es);
+      c.ws_bits_rep1.ensure(size_t(map_bytes(c) / 8 + 64));
+    }
+    max_odeg1 = rep1 ? es.max_odeg_global : es.max_odeg;
+    if (fast1) {
+      // the hop-1 expansion's tile-row table is written by k_starts_small (sized for the degree bound)
+      const int64_t eb = std::max<int64_t>(1, max_odeg1 >= 0 ? int64_t(ns) * max_odeg1 : csr1->nnz);
+      c.ws_tile_rows.ensure(size_t(std::min<int64_t>(eb, csr1->nnz + 1) / kTile + 4) * 4);
+      k_starts_small<<<1, 1024, 0, c.stream>>>(
+          k_starts, int32_t(ns), c.ht_keys.as<int64_t>(), c.ht_vals.as<int32_t>(), uint64_t(c.ht_cap - 1), c.ht_has_min,
+          c.ht_min_gidx, d_sg, rep1 ? 0 : lo, rep1 ? c.n_global : hi, csr1->row_ptr.as<int64_t>(),
+          csr1->row_ok.as<uint8_t>(), rep1 ? c.ws_bits_rep1.as<uint32_t>() : bitsA, F, c.ws_off.as<int64_t>(), K.d,
+          c.ws_tile_rows.as<int32_t>());
+      NBG_HIP(hipGetLastError());
+      nF = ns;  // an upper bound: the entries past the list have degree 0
+      return;
+    }
+    NBG_HIP(hipMemsetAsync(K.d, 0, kShardStride * kSumShards * 8, c.stream));
+    if (!ns) return;
+    const bool counted = !(s.steps == 1 && !s.distinct);
+    if (!counted) {
+      k_list_starts<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, row_ptr, row_ok, F, K.d);
+    } else {
+      if (!c.sharded && es.odeg.p) {
+        // one rank: dedup the starts through the frontier bitmap itself (a few hundred atomics)
+        // instead of marking the byte map and compacting the whole vertex space
+        NBG_HIP(hipMemsetAsync(bits16, 0, c.ws_bits_send.bytes, c.stream));
+        k_starts_bits<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, es.odeg.as<uint32_t>(), bitsA, F, K.d);
+      } else {
+        k_mark_gidx<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, map);
+        launch_compact(c, map, lo, n_own, row_ptr, row_ok, 1, F, bits16, K.d, es.odeg.as<uint32_t>());
+      }
+      if (!s.distinct)
+        k_starts_degree<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, row_ptr, row_ok, K.d + kCntHop1Rows);
+    }
+    NBG_HIP(hipGetLastError());
+    if (multi && counted) dev_allsum(c, K.d, {kCntDegSum}, K.d + kCntGlobal);
+    fetch_counters(c, K.d, multi && counted ? kCntGlobal + 4 : kCntStartWords, K.h);
+    nF = int64_t(K.h[kCntList]);
+    if (counted) {
+      E_known = int64_t(K.h[kCntDegSum]);
+      if (multi) Eg_known = int64_t(K.h[kCntGlobal]);
+      if (!s.distinct) hop1_scanned = int64_t(K.h[kCntHop1Rows]);
+    }
+  }
+
+  // the empty result: the single exit of every early return
+  int32_t finish_empty() {
+    auto h = std::make_unique<HostRows>();
+    for (auto& p : yields) {
+      h->types.push_back(result_type(p.result_type));
+      h->cols.push_back(nullptr);
+      h->str_off.push_back(nullptr);
+    }
+    fill_rows(out, std::move(h), 0, s.keep_on_device != 0);
+    hipEventRecord(c.ev[1], c.stream);
+    hipEventSynchronize(c.ev[1]);
+    float ms = 0;
+    hipEventElapsedTime(&ms, c.ev[0], c.ev[1]);
+    c.timing.total_ms = ms;
+    out->edges_scanned = c.timing.edges_scanned;
+    return NBG_OK;
+  }
+
+  // the expansions' arguments, the multi-step roots and the $- input table's upload; then the
+  // speculation's conditions (they depend on multi_root)
+  void bind_inputs() {
+    a.row_ptr = row_ptr;
+    a.col = csr.col.as<int32_t>();
+    a.lo = lo;
+    a.map = map;
+    a.err = K.d + kCntWhereErr;
+    a.storage = 0;
+    a.mark_check = 0;
+    env = make_env(c, es, csr, s.edge_type);
+    multi_root = uses_input && s.steps > 1;
+    if (multi_root) {
+      // rank of every start's vid among the distinct start vids
+      std::vector<int64_t> u(s.starts, s.starts + ns);
+      std::sort(u.begin(), u.end());
+      u.erase(std::unique(u.begin(), u.end()), u.end());
+      std::vector<int32_t> rk(size_t(std::max<int64_t>(ns, 1)));
+      for (int64_t i = 0; i < ns; i++)
+        rk[size_t(i)] = int32_t(std::lower_bound(u.begin(), u.end(), s.starts[i]) - u.begin());
+      DevBuf drk;
+      drk.alloc(rk.size() * 4);
+      NBG_HIP(hipMemcpyAsync(drk.p, rk.data(), rk.size() * 4, hipMemcpyHostToDevice, c.stream));
+      for (auto& b : root_buf) {
+        b.alloc(size_t(c.n_global + 1) * 4);
+        NBG_HIP(hipMemsetAsync(b.p, 0x7f, size_t(c.n_global + 1) * 4, c.stream));  // > every rank
+      }
+      root_tab.alloc(std::max<size_t>(u.size(), 1) * 4);
+      if (ns) k_root_init<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, drk.as<int32_t>(), ns, root_buf[0].as<int32_t>(),
+                                                             root_tab.as<int32_t>());
+      host_sync(c);  // rk is pageable host memory
+    }
+    if (uses_input) {
+      uint32_t cap = 64;
+      while (cap < uint32_t(2 * std::max<int64_t>(ns, 1))) cap <<= 1;
+      in_keys.alloc(size_t(cap) * 4);
+      in_rows.alloc(size_t(cap) * 4);
+      NBG_HIP(hipMemsetAsync(in_keys.p, 0xff, size_t(cap) * 4, c.stream));
+      NBG_HIP(hipMemsetAsync(in_rows.p, 0xff, size_t(cap) * 4, c.stream));
+      if (ns)
+        k_input_index<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, in_keys.as<int32_t>(), in_rows.as<int32_t>(),
+                                                          cap - 1);
+      NBG_HIP(hipGetLastError());
+      std::vector<PropDev> tab;
+      for (size_t i = 0; i < s.n_inputs; i++) {
+        const int32_t t = s.input_types[i];
+        const size_t w = t == NBG_T_BOOL ? 1 : 8;
+        DevBuf col, off;
+        PropDev pd{t, int32_t(w), nullptr, nullptr, nullptr, nullptr};
+        if (t != NBG_T_STRING) {
+          col.alloc(std::max<size_t>(size_t(ns) * w, 8));
+          if (ns) NBG_HIP(hipMemcpyAsync(col.p, s.input_cols[i], size_t(ns) * w, hipMemcpyHostToDevice, c.stream));
+          pd.data = col.p;
+        } else {
+          const int64_t* ho = s.input_str_offsets[i];
+          off.alloc(size_t(ns + 1) * 8);
+          NBG_HIP(hipMemcpyAsync(off.p, ho, size_t(ns + 1) * 8, hipMemcpyHostToDevice, c.stream));
+          col.alloc(size_t(ho[ns]) + 8);
+          if (ho[ns]) NBG_HIP(hipMemcpyAsync(col.p, s.input_cols[i], size_t(ho[ns]), hipMemcpyHostToDevice, c.stream));
+          pd = PropDev{t, 8, nullptr, nullptr, off.as<int64_t>(), col.as<uint8_t>()};
+        }
+        tab.push_back(pd);
+        in_cols.push_back(std::move(col));
+        in_cols.push_back(std::move(off));
+      }
+      in_tab.alloc(sizeof(PropDev) * tab.size());
+      NBG_HIP(hipMemcpyAsync(in_tab.p, tab.data(), sizeof(PropDev) * tab.size(), hipMemcpyHostToDevice, c.stream));
+      host_sync(c);  // `tab` is pageable host memory
+      env.in_keys = in_keys.as<int32_t>();
+      env.in_rows = in_rows.as<int32_t>();
+      env.in_mask = cap - 1;
+      env.iprops = in_tab.as<PropDev>();
+    }
+    host_direct = !s.keep_on_device && c.opt("host_direct", 1) != 0;
+    spec_ok = bu_ok && !multi_root && bu_force >= 0 && c.opt("bu_spec", 1) != 0;
+    spec_thr = bu_force > 0 ? 1ull : (unsigned long long)std::max<int64_t>(1, es.out_nnz_global / bu_div);
+  }
+
+  // the frontier as a list: compacts the bitmap when only that exists
+  void ensure_list() {
+    if (have_list) return;
+    cur ^= 1;
+    F = c.ws_front[cur].as<int32_t>();
+    NBG_HIP(hipMemsetAsync(K.d, 0, 8, c.stream));
+    k_bits_compact<0><<<grid_cap((n_own + 31) / 32, 1024, 4096), 1024, 0, c.stream>>>(bitsA, n_own, lo, nullptr, F,
+                                                                                     K.d + kCntList);
+    if (list_n >= 0) {
+      nF = list_n;  // counted by the compaction that wrote the bitmap: no round trip
+    } else {
+      fetch_counters(c, K.d, kCntList + 1, K.h);
+      nF = int64_t(K.h[kCntList]);
+    }
+    list_n = -1;
+    have_list = true;
+    off_ready = false;
+  }
+  // ... and its degree scan
+  void ensure_off() {
+    ensure_list();
+    if (off_ready) return;
+    E = nF ? degree_scan(c, F, nF, csr, degbuf, E_known) : 0;
+    E_known = E;
+    off_ready = true;
+  }
+  // direction choice is global (every rank must take the same branch: bottom-up allgathers)
+  bool want_bu(int64_t eg) const {  // (multi-step roots need every in-edge: top-down only)
+    return eg > 0 && bu_ok && !multi_root && bu_force >= 0 && (bu_force > 0 || eg >= es.out_nnz_global / bu_div);
+  }
+  // the start frontier's degree scan and its out-degree sum over ranks
+  void first_degrees() {
+    if (fast1) {
+      off_ready = true;  // k_starts_small wrote the scan; E is counted on the device
+      return;
+    }
+    ensure_off();
+    Eg = E;
+    if (Eg_known >= 0) Eg = Eg_known;
+    else allsum(c, &Eg, 1, K.d + kCntRed);
+  }
+  // where a DISTINCT _dst output goes: a pinned host block (host_direct) or a device block
+  void* vid_block(DevBuf& d, HostBuf& hb) {
     if (host_direct) {
       host_pool_cap(c);
       hb.release();  // (a second speculation chain in one query replaces the first's block)
@@ -3430,44 +3593,81 @@ int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
     }
     d.alloc(size_t(c.n_global + 64) * 8);
     return d.p;
-  };
-  FastPred fpk0{};
-  FastArgs fp0{};
-  bool fin_spec = false;
-  if (deferred == NBG_OK) {
-    fpk0 = has_where ? classify_pred(where, es.fields) : FastPred{};
-    if (fpk0.kind == PK_FAST) {
-      const PropCol& pc = csr.props[size_t(fpk0.col)];
-      fp0 = FastArgs{pc.data.p, pc.present.as<uint8_t>(), pc.width, fpk0.op, fpk0.k};
-    }
-    const bool ddst = s.distinct && yields.size() == 1 && yields[0].n == 1 && yields[0].ins[0].op == P_DST;
-    const bool pbu = fpk0.kind == PK_NONE ||
-                     (fpk0.kind == PK_FAST && fp0.present == nullptr && es.tr.props.size() > size_t(fpk0.col) &&
-                      es.tr.props[size_t(fpk0.col)].data.p);
-    fin_spec = ddst && pbu;
   }
-  // (several ranks: each gate reads counters summed over ranks on the device, dev_allsum, and
-  // every rank enqueues the same chain of collectives, so every rank takes the same branches)
-  const bool spec_ok = bu_ok && !multi_root && bu_force >= 0 && c.opt("bu_spec", 1) != 0;
-  const unsigned long long spec_thr =
-      bu_force > 0 ? 1ull : (unsigned long long)std::max<int64_t>(1, es.out_nnz_global / bu_div);
-  unsigned long long* const SPd = K.d + 64;
+
+  // a bottom-up hop's launches between two timing events; the hop's and its first pass's times
+  // are read later (timing_resolve) into Timing::hops[hop]
+  template <typename Fn>
+  BuLaunch timed_bu(int32_t hop, Fn launch) {
+    const size_t ia = timing_event(c);
+    BuLaunch L = launch();
+    const size_t ib = timing_event(c);
+    c.tpend.push_back(Ctx::PendingTime{ia, ib, hop, 0});
+    c.tpend.push_back(Ctx::PendingTime{ia, L.ev_first, hop, 1});
+    return L;
+  }
+  // the statistics of a bottom-up hop that ran, from its HopWord block h and its launch; a final
+  // hop (DISTINCT _dst, out_rows rows) adds its output (k_bits_compact<1>): next bits once, vid_of
+  // read + vid written
+  void record_bu_hop(const unsigned long long* h, const BuLaunch& L, bool final = false, int64_t out_rows = 0) {
+    c.timing.expand_launches++;
+    c.timing.bu_steps++;
+    const int pw = final && fpk.kind == PK_FAST ? fp.width : 0;
+    const uint64_t kb = bu_first_bytes(h, es.tr.n_rows, L.od_bytes), hb = kb + bu_rest_bytes(h, pw, L.rest_rec);
+    c.timing.expand_bytes += hb + (final ? uint64_t(es.tr.n_rows) / 8 + uint64_t(out_rows) * 16 : 0);
+    c.timing.hop(1, final, 0.0, h, 0.0, kb);
+    c.timing.name_last_hop(L.k0, L.k1, final ? "nbg::k_bits_compact<1, 8, 1>" : nullptr);
+  }
+  // the next frontier is the bitmap a bottom-up hop wrote (its HopWord block h); list_len: the
+  // bitmap's population when the hop's counts give it (ensure_list then needs no round trip)
+  void adopt_bu(const unsigned long long* h, int64_t list_len, int64_t n_global, int64_t e_global) {
+    std::swap(bitsA, bitsB);
+    have_list = false;
+    list_n = list_len;
+    off_ready = false;
+    E = int64_t(h[kHopDegSum]);
+    E_known = E;
+    nset_global = n_global;
+    Eg = e_global;
+  }
+  // the next frontier is what a compaction left (counters fetched): the list, or with lazy only
+  // the bitmap and its counted length.  whole_space (go_rep1): the compaction ran over every
+  // rank's rows, its sums are global and this rank's share sits at kCntOwnKept / kCntOwnDegSum.
+  // Several ranks otherwise: the global counts come from the first speculated hop's gate
+  // (piggy) or from dev_allsum's words.
+  void adopt_compaction(bool lazy, bool whole_space) {
+    int64_t ng = int64_t(K.h[kCntSet]), eg = int64_t(K.h[kCntDegSum]);
+    if (multi && !whole_space) {
+      const unsigned long long* g = piggy_used ? K.h + kSpecBase + kSpecSumN : K.h + kCntGlobal;
+      ng = int64_t(g[0]), eg = int64_t(g[1]);
+    }
+    nF = lazy ? 0 : int64_t(K.h[kCntList]);
+    list_n = lazy ? int64_t(K.h[whole_space ? kCntOwnKept : kCntKept]) : -1;
+    E = int64_t(K.h[whole_space ? kCntOwnDegSum : kCntDegSum]);
+    E_known = E;
+    nset_global = ng;
+    Eg = eg;
+    have_list = !lazy;
+    if (lazy) cur ^= 1;  // ensure_list flips to the list buffer again
+    off_ready = false;
+  }
+
   // enqueue the gated hops from step `first` on; the compaction behind them left its counts at
   // (e, n) and its bitmap in bitsA; hop0 = the Timing::hops index of the first one
   // several ranks (piggy): instead of (e, n), cnt = this rank's (n, e) of the compaction behind
   // the first hop; every hop's frontier allgather carries the previous hop's (n, e) of every rank
-  // to its gate (GateIn::all), one exchange per hop instead of an allgather and an all-reduce
-  bool spec_blocks_used = false;
+  // to its gate (GateIn::all)
   // fb_first (several ranks, go_rep1): the first hop reads this whole-space frontier and (e, n)
   // summed over ranks already; the hops after it exchange as with cnt
-  auto spec_enqueue = [&](int32_t first, const unsigned long long* e, const unsigned long long* n, int32_t hop0,
-                          const unsigned long long* cnt = nullptr, const uint32_t* fb_first = nullptr) {
+  void spec_enqueue(int32_t first, const unsigned long long* e, const unsigned long long* n, int32_t hop0,
+                    const unsigned long long* cnt = nullptr, const uint32_t* fb_first = nullptr) {
     spec.clear();
     if (!spec_ok) return;
+    unsigned long long* const SPd = K.d + kSpecBase;
     // the blocks start at zero (query start); a second chain in one query reuses them
     if (spec_blocks_used) {
       clean_shards();
-      NBG_HIP(hipMemsetAsync(SPd, 0, 16 * 12 * 8, c.stream));
+      NBG_HIP(hipMemsetAsync(SPd, 0, kSpecWords * kMaxSpec * 8, c.stream));
     }
     spec_blocks_used = true;
     if (ks > 1) shards_dirty = true;
@@ -3475,11 +3675,11 @@ int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
     uint32_t* outb = bitsB;
     const unsigned long long* pg = nullptr;
     unsigned long long* last_blk = nullptr;
-    for (int32_t st = first; st <= s.steps && spec.size() < 12; st++) {
+    for (int32_t st = first; st <= s.steps && spec.size() < size_t(kMaxSpec); st++) {
       const bool fin = st == s.steps;
       if (fin && !fin_spec) break;
-      unsigned long long* blk = SPd + 16 * spec.size();
-      // the hop's first pass evaluates its gate (GateIn) and publishes it at blk[8]
+      unsigned long long* blk = SPd + kSpecWords * spec.size();
+      // the hop's first pass evaluates its gate (GateIn) and publishes it at kSpecGate
       GateIn gi;
       gi.e = e, gi.n = n, gi.pg = pg, gi.thr = spec_thr;
       gi.shards = ks;  // (several ranks: ks = 1)
@@ -3498,67 +3698,66 @@ int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
       } else {
         fb = global_bits(c, in);
       }
-      const size_t ia = timing_event(c);
-      size_t ik;
-      if (!fin) {
-        ik = launch_bu_lean(c, es, fb, outb, es.odeg.as<uint32_t>(), PK_NONE, fp, -1, blk, true, blk + 8, gi, true, ks);
-      } else {
-        FastArgs tfp = fp0;
-        if (fpk0.kind == PK_FAST) tfp.data = es.tr.props[size_t(fpk0.col)].data.p;
-        ik = launch_bu_lean(c, es, fb, outb, nullptr, fpk0.kind, tfp, fpk0.kind == PK_FAST ? fpk0.col : -1, blk, true,
-                            blk + 8, gi, true, ks);
-        void* vout = vid_block(spec_vids, spec_hvids);
-        launch_bits_vids(c, outb, es.tr.n_rows, lo, vout, blk + 9, blk + 8);
-      }
-      NBG_HIP(hipGetLastError());
-      const size_t ib = timing_event(c);
-      c.tpend.push_back(Ctx::PendingTime{ia, ib, hop, 0});
-      c.tpend.push_back(Ctx::PendingTime{ia, ik, hop, 1});
-      spec.push_back(Spec{hop, fin, c.bu_kernel_name, c.bu_rest_name});
-      e = blk + 1;
-      n = blk + 0;
+      BuLaunch L = timed_bu(hop, [&] {
+        BuLaunch l;
+        if (!fin) {
+          l = launch_bu_lean(c, es, fb, outb, es.odeg.as<uint32_t>(), PK_NONE, no_fp, -1, blk, true, blk + kSpecGate,
+                             gi, true, ks);
+        } else {
+          FastArgs tfp = fp;
+          if (fpk.kind == PK_FAST) tfp.data = es.tr.props[size_t(fpk.col)].data.p;
+          l = launch_bu_lean(c, es, fb, outb, nullptr, fpk.kind, tfp, fpk.kind == PK_FAST ? fpk.col : -1, blk, true,
+                             blk + kSpecGate, gi, true, ks);
+          void* vout = vid_block(spec_vids, spec_hvids);
+          launch_bits_vids(c, outb, es.tr.n_rows, lo, vout, blk + kSpecRows, blk + kSpecGate);
+        }
+        NBG_HIP(hipGetLastError());
+        return l;
+      });
+      spec.push_back(Spec{hop, fin, std::move(L)});
+      e = blk + kHopDegSum;
+      n = blk + kHopFound;
       last_blk = fin ? nullptr : blk;
       if (cnt || fb_first) {
         cnt = blk;  // the next hop's exchange carries this hop's (n, e)
       } else if (multi && !fin) {
-        dev_allsum(c, blk, {0, 1}, blk + 10);
-        e = blk + 11;
-        n = blk + 10;
+        dev_allsum(c, blk, {kHopFound, kHopDegSum}, blk + kSpecSumN);
+        e = blk + kSpecSumE;
+        n = blk + kSpecSumN;
       }
-      pg = blk + 8;
+      pg = blk + kSpecGate;
       const uint32_t* t = in;
       in = outb;
       outb = const_cast<uint32_t*>(t);
     }
-    // (piggy) a chain ending on a non-final hop: its global counts for the host, at blk[12, 14)
-    if (cnt && last_blk) dev_allsum(c, last_blk, {0, 1}, last_blk + 12);
-  };
+    // (piggy) a chain ending on a non-final hop: its global counts for the host
+    if (cnt && last_blk) dev_allsum(c, last_blk, {kHopFound, kHopDegSum}, last_blk + kSpecLastN);
+  }
   // several ranks: the global (n, e) of speculated hop j after the fetch -- piggy: published by
-  // hop j + 1's gate (its block's [10, 12)) or, for the chain's last hop, at [12, 14); else [10, 12)
-  auto spec_global = [&](size_t j, bool piggy, unsigned long long& ng, unsigned long long& eg) {
-    const unsigned long long* hh = K.h + 64 + 16 * j;
-    if (!piggy) {
-      ng = hh[10], eg = hh[11];
+  // hop j + 1's gate (its block's kSpecSumN / kSpecSumE) or, for the chain's last hop, at
+  // kSpecLastN / kSpecLastE; else its own block's kSpecSumN / kSpecSumE
+  void spec_global(size_t j, unsigned long long& ng, unsigned long long& eg) const {
+    const unsigned long long* hh = K.h + kSpecBase + kSpecWords * j;
+    if (!piggy_used) {
+      ng = hh[kSpecSumN], eg = hh[kSpecSumE];
     } else if (j + 1 < spec.size()) {
-      ng = hh[16 + 10], eg = hh[16 + 11];
+      ng = hh[kSpecWords + kSpecSumN], eg = hh[kSpecWords + kSpecSumE];
     } else {
-      ng = hh[12], eg = hh[13];
+      ng = hh[kSpecLastN], eg = hh[kSpecLastE];
     }
-  };
-  bool piggy_used = false;
-  auto spec_words = [&](int base) { return spec.empty() ? base : 64 + 16 * int(spec.size()); };
-  auto spec_final = [&]() { return !spec.empty() && spec.back().final; };
-  // after the fetch: record the hops that ran, as the bottom-up branch below does; stops at the
-  // first gate that was 0 (its timings dropped).  Returns the steps consumed; *fin_done when the
-  // final step ran (its counters copied to fin_h)
-  unsigned long long fin_h[16] = {};
-  std::string fin_k0, fin_k1;
-  bool fin_done = false;
-  auto spec_replay = [&]() -> int32_t {
+  }
+  // the words a fetch behind an enqueued chain reads (base: without one)
+  int spec_words(int base) const { return spec.empty() ? base : kSpecBase + kSpecWords * int(spec.size()); }
+  // (the device work ends at the fetch when the speculated final hop runs: ev[1] ahead of it)
+  hipEvent_t spec_final_event() const { return !spec.empty() && spec.back().final && tot_ev ? c.ev[1] : nullptr; }
+  // after the fetch: record the hops that ran, as hop_bottom_up does; stops at the first gate
+  // that was 0 (its timings dropped).  Returns the steps consumed; fin_done when the final step
+  // ran (its block copied to fin_h)
+  int32_t spec_replay() {
     int32_t used = 0;
     for (size_t j = 0; j < spec.size(); j++) {
-      const unsigned long long* hh = K.h + 64 + 16 * j;
-      if (hh[8] == 0) {
+      const unsigned long long* hh = K.h + kSpecBase + kSpecWords * j;
+      if (hh[kSpecGate] == 0) {
         const int32_t cut = spec[j].hop;
         c.tpend.erase(std::remove_if(c.tpend.begin(), c.tpend.end(),
                                      [cut](const Ctx::PendingTime& p) { return p.hop >= cut; }),
@@ -3567,477 +3766,357 @@ int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
       }
       c.timing.spec_hops++;
       if (spec[j].final) {
-        std::copy(hh, hh + 16, fin_h);
-        fin_k0 = spec[j].k0;
-        fin_k1 = spec[j].k1;
+        std::copy(hh, hh + kSpecWords, fin_h);
+        fin_L = spec[j].L;
         fin_done = true;
         break;
       }
       c.timing.steps_run++;
       c.timing.edges_scanned += uint64_t(E);
-      c.timing.expand_launches++;
-      c.timing.bu_steps++;
-      const uint64_t kb = bu_first_bytes(hh, es.tr.n_rows, c.bu_od_bytes), hb = kb + bu_rest_bytes(hh, 0, c.bu_rest_rec);
-      c.timing.expand_bytes += hb;
-      c.timing.hop(1, false, 0.0, hh, 0.0, kb);
-      c.timing.name_last_hop(spec[j].k0, spec[j].k1);
-      std::swap(bitsA, bitsB);
-      have_list = false;
-      list_n = -1;
-      off_ready = false;
-      E = int64_t(hh[1]);
-      E_known = E;
-      nset_global = int64_t(hh[0]);
-      Eg = E;
-      if (multi) {
-        unsigned long long ng, eg;
-        spec_global(j, piggy_used, ng, eg);
-        nset_global = int64_t(ng);
-        Eg = int64_t(eg);
-      }
+      record_bu_hop(hh, spec[j].L);
+      unsigned long long ng = hh[kHopFound], eg = hh[kHopDegSum];
+      if (multi) spec_global(j, ng, eg);
+      adopt_bu(hh, -1, int64_t(ng), int64_t(eg));
       used++;
       if (nset_global == 0) break;  // the caller returns the empty result
     }
     spec.clear();
     return used;
-  };
-  if (fast1) {
-    off_ready = true;  // k_starts_small wrote the scan; E is counted on the device
-  } else {
-    ensure_off();
-    Eg = E;
-    if (Eg_known >= 0) Eg = Eg_known;
-    else allsum(c, &Eg, 1, red);
   }
-  for (int32_t step = 1; step < s.steps; step++) {
-    c.timing.steps_run++;
-    clean_shards();  // (the speculated hops' sums were fetched: dense counters from here on)
-    if (fast1 && step == 1) {
-      // the first hop top-down from k_starts_small's list (nF = ns bounds it), compaction, then
-      // one round trip for the start counts and the next frontier's together
-      a.F = F;
-      a.nF = nF;
-      a.off = c.ws_off.as<int64_t>();
-      const int64_t e_bound = std::max<int64_t>(1, max_odeg1 >= 0 ? ns * max_odeg1 : csr1.nnz);
-      ExpandArgs a1 = a;
-      if (rep1) a1.row_ptr = csr1.row_ptr.as<int64_t>(), a1.col = csr1.col.as<int32_t>(), a1.lo = 0;
-      launch_expand<EXP_MARK>(c, a1, PK_NONE, fp, nullptr, env, std::min<int64_t>(e_bound, csr1.nnz + 1), starts_tiles);
-      cur ^= 1;
-      F = c.ws_front[cur].as<int32_t>();
-      const bool lazy = bu_ok && c.opt("compact_list", 0) == 0;
-      // (K.d[0, 256) are zero: k_starts_small cleared the counters)
-      if (rep1) {
-        // the whole-space frontier and its counts (the same on every rank), plus this rank's share
-        // (K.d[15, 17)) and its owned slice in bitsA (for a host-chosen top-down hop 2).  (Block
-        // partials + a reduce launch instead of the block atomics measured the same: 0.4255 vs
-        // 0.4243 ms a one-rank RCCL query, profiles/r13b_*)
-        launch_compact(c, map, 0, c.n_global, csr1.row_ptr.as<int64_t>(), csr1.row_ok.as<uint8_t>(), 1, nullptr,
-                       c.ws_bits_rep1.as<uint16_t>(), K.d, es.rep_odeg.as<uint32_t>(), true, 1, lo, hi,
-                       reinterpret_cast<uint16_t*>(bitsA));
-      } else if (multi && lazy && es.odeg.p) {
-        // several ranks: every owner ORs the marks it receives straight into its frontier bitmap
-        exchange_marks(c, map, bitsA, es.odeg.as<uint32_t>(), K.d + 12);
-      } else {
-        exchange_marks(c, map);  // several ranks: every owner receives the marks of its vertices
-        launch_compact(c, map, lo, n_own, row_ptr, row_ok, 1, lazy ? nullptr : F, reinterpret_cast<uint16_t*>(bitsA),
-                       K.d, es.odeg.as<uint32_t>(), true, ks, 0, -1, nullptr, map_bound);
-        if (ks > 1) shards_dirty = true;
-      }
-      // several ranks: the counts over ranks -- piggy: carried by the first speculated hop's
-      // frontier exchange (its gate publishes them); else found, next out-degree sum and hop-1
-      // entries summed into K.d[48, 51)
-      piggy_used = multi && spec_ok && (rep1 || c.opt("comm_piggy", 1) != 0);
-      if (multi && !piggy_used) dev_allsum(c, K.d, {12, 13, 41}, K.d + 48);
-      if (rep1)
-        spec_enqueue(2, K.d + 13, K.d + 12, c.timing.n_hops + 1, nullptr, c.ws_bits_rep1.as<uint32_t>());
-      else
-        spec_enqueue(2, K.d + (multi ? 49 : 13), K.d + (multi ? 48 : 12), c.timing.n_hops + 1,
-                     piggy_used ? K.d + 12 : nullptr);  // (hop 1: below)
-      if (piggy_used && spec.empty()) {  // nothing speculated (steps == 2 without the final): sum here
-        piggy_used = false;
-        if (!rep1) dev_allsum(c, K.d, {12, 13, 41}, K.d + 48);
-      }
-      // (the device work ends here when the speculated final hop runs: ev[1] ahead of the fetch)
-      fetch_counters(c, K.d, spec_words(multi ? 52 : 42), K.h, spec_final() && tot_ev ? c.ev[1] : nullptr, ks);
-      const int64_t nF1 = int64_t(K.h[40]), E1 = int64_t(K.h[41]);
-      if (!s.distinct) hop1_scanned = int64_t(K.h[30]);
-      // (go_rep1: every rank ran the whole hop; rank 0 counts it, so the ranks' sum is the hop's)
-      if (!rep1 || c.rank == 0) c.timing.edges_scanned += uint64_t(hop1_scanned >= 0 ? hop1_scanned : E1);
-      if (E1 > 0) c.timing.expand_bytes += expand_bytes(nF1, E1, 0, EXP_MARK);
-      const unsigned long long hs[8] = {(unsigned long long)nF1, (unsigned long long)E1, 0, 0, 0, 0, 0, 0};
-      c.timing.hop(0, false, 0.0, hs);
-      int64_t n1g = int64_t(K.h[12]), e1g = int64_t(K.h[13]), E1g = E1;
-      if (rep1) {
-        // (whole-space counts: already the sums over ranks)
-      } else if (multi && piggy_used) {  // the first speculated hop's gate published hop 1's sums
-        n1g = int64_t(K.h[64 + 10]);
-        e1g = int64_t(K.h[64 + 11]);
-        E1g = n1g;  // (no marks anywhere iff no start has out-edges: the empty result either way)
-      } else if (multi) {
-        n1g = int64_t(K.h[48]);
-        e1g = int64_t(K.h[49]);
-        E1g = int64_t(K.h[50]);
-      }
-      if (E1g == 0) return finish_empty();  // every start lacks out-edges
-      nF = lazy ? 0 : int64_t(K.h[0]);
-      list_n = lazy ? int64_t(K.h[rep1 ? 15 : 14]) : -1;
-      E = int64_t(K.h[rep1 ? 16 : 13]);
-      E_known = E;
-      nset_global = n1g;
-      Eg = e1g;
-      have_list = !lazy;
-      if (lazy) cur ^= 1;  // ensure_list flips to the list buffer again
-      off_ready = false;
-      if (nset_global == 0) return finish_empty();  // onEmptyInputs (GoExecutor.cpp:392-395)
-      step += spec_replay();
-      if (nset_global == 0) return finish_empty();
-      if (fin_done) break;
-      continue;
-    }
-    c.timing.edges_scanned += uint64_t(step == 1 && hop1_scanned >= 0 ? hop1_scanned : E);
-    if (Eg == 0) return finish_empty();  // every frontier vertex lacks out-edges
-    if (want_bu(Eg)) {
-      // bottom-up: frontier bitmap in, next frontier bitmap out
-      const Csr& tr = es.tr;
-      const uint32_t* fb = global_bits(c, bitsA);
-      const size_t ia = timing_event(c);
-      const size_t ik = launch_bu_lean(c, es, fb, bitsB, es.odeg.as<uint32_t>(), PK_NONE, fp, -1, K.d, step > 1);
-      const size_t ib = timing_event(c);
-      c.tpend.push_back(Ctx::PendingTime{ia, ib, c.timing.n_hops, 0});
-      c.tpend.push_back(Ctx::PendingTime{ia, ik, c.timing.n_hops, 1});
-      if (multi) dev_allsum(c, K.d, {0, 1}, K.d + 48);
-      fetch_counters(c, K.d, multi ? 50 : 8, K.h);
-      c.timing.expand_launches++;
-      c.timing.bu_steps++;
-      const uint64_t kb = bu_first_bytes(K.h, tr.n_rows, c.bu_od_bytes), hb = kb + bu_rest_bytes(K.h, 0, c.bu_rest_rec);
-      c.timing.expand_bytes += hb;
-      c.timing.hop(1, false, 0.0, K.h, 0.0, kb);
-      c.timing.name_last_hop(c.bu_kernel_name, c.bu_rest_name);
-      std::swap(bitsA, bitsB);
-      have_list = false;
-      // one rank: the found rows the two passes counted are the new bitmap's population (every
-      // found row sets one bit; pending rows are disjoint from the first pass's found rows), so
-      // ensure_list needs no round trip; several ranks: the local population is read back
-      list_n = multi ? -1 : int64_t(K.h[0]);
-      off_ready = false;
-      E = int64_t(K.h[1]);
-      E_known = E;
-      nset_global = multi ? int64_t(K.h[48]) : int64_t(K.h[0]);
-      Eg = multi ? int64_t(K.h[49]) : E;
+
+  // hop 1 of a small start set: top-down from k_starts_small's list (nF = ns bounds it),
+  // compaction, then one round trip for the start counts and the next frontier's together.
+  // false: every start lacks out-edges (the empty result)
+  bool hop1_small() {
+    frontier_args();
+    const int64_t e_bound = std::max<int64_t>(1, max_odeg1 >= 0 ? ns * max_odeg1 : csr1->nnz);
+    ExpandArgs a1 = a;
+    if (rep1) a1.row_ptr = csr1->row_ptr.as<int64_t>(), a1.col = csr1->col.as<int32_t>(), a1.lo = 0;
+    // (the tile-row table: written by k_starts_small)
+    launch_expand<EXP_MARK>(c, a1, PK_NONE, no_fp, nullptr, env, std::min<int64_t>(e_bound, csr1->nnz + 1), true);
+    cur ^= 1;
+    F = c.ws_front[cur].as<int32_t>();
+    const bool lazy = bu_ok && c.opt("compact_list", 0) == 0;
+    // (the counter block is zero: k_starts_small cleared it)
+    if (rep1) {
+      // the whole-space frontier and its counts (the same on every rank), plus this rank's share
+      // (kCntOwnKept, kCntOwnDegSum) and its owned slice in bitsA (for a host-chosen top-down hop
+      // 2).  (Block partials + a reduce launch instead of the block atomics measured the same:
+      // 0.4255 vs 0.4243 ms a one-rank RCCL query, profiles/r13b_*)
+      launch_compact(c, map, 0, c.n_global, csr1->row_ptr.as<int64_t>(), csr1->row_ok.as<uint8_t>(), 1, nullptr,
+                     c.ws_bits_rep1.as<uint16_t>(), K.d, es.rep_odeg.as<uint32_t>(), true, 1, lo, hi,
+                     reinterpret_cast<uint16_t*>(bitsA));
+    } else if (multi && lazy && es.odeg.p) {
+      // several ranks: every owner ORs the marks it receives straight into its frontier bitmap
+      exchange_marks(c, map, bitsA, es.odeg.as<uint32_t>(), K.d + kCntSet);
     } else {
-      ensure_off();
-      a.F = F;
-      a.nF = nF;
-      a.off = c.ws_off.as<int64_t>();
-      const double ms0 = c.timing.expand_ms;
-      if (multi_root) {
-        NBG_HIP(hipMemsetAsync(root_buf[root_cur ^ 1].p, 0x7f, size_t(c.n_global + 1) * 4, c.stream));
-        a.root_cur = root_buf[root_cur].as<int32_t>();
-        a.root_next = root_buf[root_cur ^ 1].as<int32_t>();
-      }
-      if (E > 0) {
-        launch_expand<EXP_MARK>(c, a, PK_NONE, fp, nullptr, env, E);
-        c.timing.expand_bytes += expand_bytes(nF, E, 0, EXP_MARK);
-      }
-      if (multi_root) {
-        exchange_roots(c, a.root_next);
-        root_cur ^= 1;
-        a.root_cur = nullptr;
-        a.root_next = nullptr;
-      }
-      const unsigned long long hs[8] = {(unsigned long long)nF, (unsigned long long)E, 0, 0, 0, 0, 0, 0};
-      c.timing.hop(0, false, c.timing.expand_ms - ms0, hs);
-      exchange_marks(c, map);
-      // next frontier = set of dsts (P12): compact, drop rows without out-edges, bitmap too
-      cur ^= 1;
-      F = c.ws_front[cur].as<int32_t>();
-      NBG_HIP(hipMemsetAsync(K.d, 0, 32, c.stream));
-      // when the next hop may go bottom-up it reads the bitmap alone: the list is left to
-      // ensure_list (option compact_list = 1 always writes it here).  One rank only: this
-      // bitmap is slice-relative, ensure_list's input is the bottom-up's global-indexed one
-      const bool lazy = bu_ok && !multi_root && c.opt("compact_list", 0) == 0;
+      exchange_marks(c, map);  // several ranks: every owner receives the marks of its vertices
       launch_compact(c, map, lo, n_own, row_ptr, row_ok, 1, lazy ? nullptr : F, reinterpret_cast<uint16_t*>(bitsA),
-                     K.d, es.odeg.as<uint32_t>(), false, 1, 0, -1, nullptr, map_bound);
-      piggy_used = multi && lazy && spec_ok && c.opt("comm_piggy", 1) != 0;
-      if (multi && !piggy_used) dev_allsum(c, K.d, {12, 13}, K.d + 48);
-      if (lazy)
-        spec_enqueue(step + 1, K.d + (multi ? 49 : 13), K.d + (multi ? 48 : 12), c.timing.n_hops,
-                     piggy_used ? K.d + 12 : nullptr);
-      if (piggy_used && spec.empty()) {
-        piggy_used = false;
-        dev_allsum(c, K.d, {12, 13}, K.d + 48);
-      }
-      fetch_counters(c, K.d, spec_words(multi ? 50 : 16), K.h, spec_final() && tot_ev ? c.ev[1] : nullptr, ks);
-      nF = lazy ? 0 : int64_t(K.h[0]);
-      list_n = lazy ? int64_t(K.h[14]) : -1;
-      E = int64_t(K.h[13]);
-      E_known = E;
-      nset_global = int64_t(K.h[12]);
-      Eg = E;
-      if (multi) {
-        nset_global = int64_t(piggy_used ? K.h[64 + 10] : K.h[48]);
-        Eg = int64_t(piggy_used ? K.h[64 + 11] : K.h[49]);
-      }
-      have_list = !lazy;
-      if (lazy) cur ^= 1;  // ensure_list flips to the list buffer again
-      off_ready = false;
+                     K.d, es.odeg.as<uint32_t>(), true, ks, 0, -1, nullptr, map_bound);
+      if (ks > 1) shards_dirty = true;
     }
-    if (nset_global == 0) return finish_empty();  // onEmptyInputs (GoExecutor.cpp:392-395)
-    if (!spec.empty()) {
-      step += spec_replay();
-      if (nset_global == 0) return finish_empty();
-      if (fin_done) break;
+    // several ranks: the counts over ranks -- piggy: carried by the first speculated hop's
+    // frontier exchange (its gate publishes them); else found, next out-degree sum and hop-1
+    // entries summed into [kCntGlobal, kCntGlobal + 3)
+    piggy_used = multi && spec_ok && (rep1 || c.opt("comm_piggy", 1) != 0);
+    if (multi && !piggy_used) dev_allsum(c, K.d, {kCntSet, kCntDegSum, kCntStartsE}, K.d + kCntGlobal);
+    if (rep1)
+      spec_enqueue(2, K.d + kCntDegSum, K.d + kCntSet, c.timing.n_hops + 1, nullptr, c.ws_bits_rep1.as<uint32_t>());
+    else
+      spec_enqueue(2, K.d + (multi ? kCntGlobal + 1 : kCntDegSum), K.d + (multi ? kCntGlobal : kCntSet),
+                   c.timing.n_hops + 1, piggy_used ? K.d + kCntSet : nullptr);  // (hop 1: below)
+    if (piggy_used && spec.empty()) {  // nothing speculated (steps == 2 without the final): sum here
+      piggy_used = false;
+      if (!rep1) dev_allsum(c, K.d, {kCntSet, kCntDegSum, kCntStartsE}, K.d + kCntGlobal);
     }
+    fetch_counters(c, K.d, spec_words(multi ? kCntGlobal + 4 : kCntStartsE + 1), K.h, spec_final_event(), ks);
+    const int64_t nF1 = int64_t(K.h[kCntStartsN]), E1 = int64_t(K.h[kCntStartsE]);
+    if (!s.distinct) hop1_scanned = int64_t(K.h[kCntHop1Rows]);
+    // (go_rep1: every rank ran the whole hop; rank 0 counts it, so the ranks' sum is the hop's)
+    if (!rep1 || c.rank == 0) c.timing.edges_scanned += uint64_t(hop1_scanned >= 0 ? hop1_scanned : E1);
+    if (E1 > 0) c.timing.expand_bytes += expand_bytes(nF1, E1, 0, EXP_MARK);
+    record_td_hop(false, 0.0, nF1, E1);
+    // hop 1's entries over ranks (go_rep1: whole-space counts, already the sums)
+    int64_t E1g = E1;
+    if (multi && !rep1)  // (piggy: no marks anywhere iff no start has out-edges: the empty result either way)
+      E1g = int64_t(piggy_used ? K.h[kSpecBase + kSpecSumN] : K.h[kCntGlobal + 2]);
+    if (E1g == 0) return false;
+    adopt_compaction(lazy, rep1);
+    return true;
   }
-  // ---- final step ----
-  c.timing.steps_run++;
-  if (!fin_done) clean_shards();
-  if (multi_root) {
-    env.in_root = root_buf[root_cur].as<int32_t>();
-    env.in_root_tab = root_tab.as<int32_t>();
+
+  // a host-chosen bottom-up hop: frontier bitmap in, next frontier bitmap out
+  void hop_bottom_up(int32_t step) {
+    const uint32_t* fb = global_bits(c, bitsA);
+    const BuLaunch L = timed_bu(c.timing.n_hops, [&] {
+      return launch_bu_lean(c, es, fb, bitsB, es.odeg.as<uint32_t>(), PK_NONE, no_fp, -1, K.d, step > 1);
+    });
+    if (multi) dev_allsum(c, K.d, {kHopFound, kHopDegSum}, K.d + kCntGlobal);
+    fetch_counters(c, K.d, multi ? kCntGlobal + 2 : kHopWords, K.h);
+    record_bu_hop(K.h, L);
+    // one rank: the found rows the two passes counted are the new bitmap's population (every
+    // found row sets one bit; pending rows are disjoint from the first pass's found rows), so
+    // ensure_list needs no round trip; several ranks: the local population is read back
+    if (multi) adopt_bu(K.h, -1, int64_t(K.h[kCntGlobal]), int64_t(K.h[kCntGlobal + 1]));
+    else adopt_bu(K.h, int64_t(K.h[kHopFound]), int64_t(K.h[kHopFound]), int64_t(K.h[kHopDegSum]));
   }
-  if (deferred != NBG_OK) throw Error(deferred, deferred_msg);
-  FastPred fpk = has_where ? classify_pred(where, es.fields) : FastPred{};
-  int pk = fpk.kind;
-  if (pk == PK_FAST) {
-    const PropCol& pc = csr.props[size_t(fpk.col)];
-    fp = FastArgs{pc.data.p, pc.present.as<uint8_t>(), pc.width, fpk.op, fpk.k};
+
+  // the frontier list and its degree scan as the expansion's arguments
+  void frontier_args() {
+    a.F = F;
+    a.nF = nF;
+    a.off = c.ws_off.as<int64_t>();
   }
-  DevBuf dprog;
-  // DISTINCT _dst reads no YIELD program (and the WHERE program only on the VM path)
-  const bool lone_dst_distinct = s.distinct && yields.size() == 1 && yields[0].n == 1 && yields[0].ins[0].op == P_DST;
-  if (pk == PK_VM || (!default_yield && !lone_dst_distinct)) {
-    dprog.alloc(sizeof(Program) * (yields.size() + 1));
-    c.h2d(dprog.p, &where, sizeof(Program));
-    c.h2d(dprog.as<Program>() + 1, yields.data(), sizeof(Program) * yields.size());
+  // a top-down hop's statistics (frontier entries, edges, rows out)
+  void record_td_hop(bool final, double ms, int64_t n, int64_t e, int64_t rows_out = 0) {
+    const unsigned long long hs[8] = {(unsigned long long)n, (unsigned long long)e, uint64_t(rows_out), 0, 0, 0, 0, 0};
+    c.timing.hop(0, final, ms, hs);
   }
-  int pred_w = pk == PK_FAST ? fp.width : 0;
-  c.timing.edges_scanned += uint64_t(E);
-  bool distinct_dst = s.distinct && yields.size() == 1 && yields[0].n == 1 && yields[0].ins[0].op == P_DST;
-  auto* h = new HostRows();
-  int64_t nrows = 0;
-  std::vector<DevBuf> slen(yields.size());  // STRING yield columns: byte length per row
-  std::map<size_t, bool> host_cols;         // columns already in pinned host memory (host_direct)
-  try {
-    if (distinct_dst) {
-      // DISTINCT e._dst: mark surviving dsts, compact the whole vertex space (no deg filter).
-      // Bottom-up only when the predicate cannot error (the reference fails the query on any
-      // row's eval error, so every row must be evaluated when errors are possible).
-      bool pred_bu = pk == PK_NONE || (pk == PK_FAST && fp.present == nullptr &&
-                                       es.tr.props.size() > size_t(fpk.col) && es.tr.props[size_t(fpk.col)].data.p);
-      bool bu = pred_bu && want_bu(Eg);
-      DevBuf vids;
-      HostBuf hvids;
-      void* vout = nullptr;
-      if (fin_done) {
-        // the speculated final hop ran (spec_replay): its counters, rows and kernel names
-        vids = std::move(spec_vids);
-        hvids = std::move(spec_hvids);
-        c.timing.expand_launches++;
-        c.timing.bu_steps++;
-        nrows = int64_t(fin_h[9]);
-        const int pw = pk == PK_FAST ? fp.width : 0;
-        const uint64_t kb = bu_first_bytes(fin_h, es.tr.n_rows, 0), hb = kb + bu_rest_bytes(fin_h, pw, c.bu_rest_rec);
-        c.timing.expand_bytes += hb + uint64_t(es.tr.n_rows) / 8 + uint64_t(nrows) * 16;
-        c.timing.hop(1, true, 0.0, fin_h, 0.0, kb);
-        c.timing.name_last_hop(fin_k0, fin_k1, "nbg::k_bits_compact<1, 8, 1>");
-      } else {
-        vout = nullptr;
-      }
-      if (fin_done) {
-      } else if (bu) {
-        FastArgs tfp = fp;
-        if (pk == PK_FAST) tfp.data = es.tr.props[size_t(fpk.col)].data.p;
-        const Csr& tr = es.tr;
-        NBG_HIP(hipMemsetAsync(K.d, 0, 8, c.stream));
-        const uint32_t* fb = global_bits(c, bitsA);
-        const size_t ia = timing_event(c);
-        const size_t ik =
-            launch_bu_lean(c, es, fb, bitsB, nullptr, pk, tfp, pk == PK_FAST ? fpk.col : -1, K.d + 8, s.steps > 1);
-        vout = vid_block(vids, hvids);
-        launch_bits_vids(c, bitsB, tr.n_rows, lo, vout, K.d, nullptr);
+  // a top-down expansion into the byte map, the marks exchanged to their owners; the final one
+  // evaluates the WHERE, the others carry the multi-step roots along
+  void expand_marks(bool final) {
+    ensure_off();
+    frontier_args();
+    const double ms0 = c.timing.expand_ms;
+    const bool roots = multi_root && !final;
+    if (roots) {
+      NBG_HIP(hipMemsetAsync(root_buf[root_cur ^ 1].p, 0x7f, size_t(c.n_global + 1) * 4, c.stream));
+      a.root_cur = root_buf[root_cur].as<int32_t>();
+      a.root_next = root_buf[root_cur ^ 1].as<int32_t>();
+    }
+    if (E > 0) {
+      if (final) launch_expand<EXP_MARK>(c, a, fpk.kind, fp, dprog.as<Program>(), env, E);
+      else launch_expand<EXP_MARK>(c, a, PK_NONE, no_fp, nullptr, env, E);
+      c.timing.expand_bytes += expand_bytes(nF, E, final ? pred_w() : 0, EXP_MARK);
+    }
+    if (roots) {
+      exchange_roots(c, a.root_next);
+      root_cur ^= 1;
+      a.root_cur = nullptr;
+      a.root_next = nullptr;
+    }
+    record_td_hop(final, c.timing.expand_ms - ms0, nF, E);
+    exchange_marks(c, map);
+  }
+
+  // a top-down hop: expansion into the byte map, compaction to the next frontier, and the
+  // remaining hops speculated behind it
+  void hop_top_down(int32_t step) {
+    expand_marks(false);
+    // next frontier = set of dsts (P12): compact, drop rows without out-edges, bitmap too
+    cur ^= 1;
+    F = c.ws_front[cur].as<int32_t>();
+    NBG_HIP(hipMemsetAsync(K.d, 0, 32, c.stream));
+    // when the next hop may go bottom-up it reads the bitmap alone: the list is left to
+    // ensure_list (option compact_list = 1 always writes it here).  One rank only: this
+    // bitmap is slice-relative, ensure_list's input is the bottom-up's global-indexed one
+    const bool lazy = bu_ok && !multi_root && c.opt("compact_list", 0) == 0;
+    launch_compact(c, map, lo, n_own, row_ptr, row_ok, 1, lazy ? nullptr : F, reinterpret_cast<uint16_t*>(bitsA),
+                   K.d, es.odeg.as<uint32_t>(), false, 1, 0, -1, nullptr, map_bound);
+    piggy_used = multi && lazy && spec_ok && c.opt("comm_piggy", 1) != 0;
+    if (multi && !piggy_used) dev_allsum(c, K.d, {kCntSet, kCntDegSum}, K.d + kCntGlobal);
+    if (lazy)
+      spec_enqueue(step + 1, K.d + (multi ? kCntGlobal + 1 : kCntDegSum), K.d + (multi ? kCntGlobal : kCntSet),
+                   c.timing.n_hops, piggy_used ? K.d + kCntSet : nullptr);
+    if (piggy_used && spec.empty()) {
+      piggy_used = false;
+      dev_allsum(c, K.d, {kCntSet, kCntDegSum}, K.d + kCntGlobal);
+    }
+    fetch_counters(c, K.d, spec_words(multi ? kCntGlobal + 2 : kCntOwnKept + 1), K.h, spec_final_event(), ks);
+    adopt_compaction(lazy, false);
+  }
+
+  int pred_w() const { return fpk.kind == PK_FAST ? fp.width : 0; }
+  // WHERE / YIELD evaluation errors of the final step (summed over ranks): the reference fails
+  // the query on any row's error
+  void check_eval_errors(int word, const char* what) {
+    if (multi) dev_allsum(c, K.d, {word}, K.d + kCntGlobal);
+    fetch_counters(c, K.d, multi ? kCntGlobal + 1 : kCntYieldErr + 1, K.h);
+    if (K.h[multi ? kCntGlobal : word]) throw Error(NBG_E_EVAL, what);
+  }
+
+  // the final step begins: the deferred compile error, the programs' upload, the result's owner
+  void begin_final() {
+    if (multi_root) {
+      env.in_root = root_buf[root_cur].as<int32_t>();
+      env.in_root_tab = root_tab.as<int32_t>();
+    }
+    if (deferred != NBG_OK) throw Error(deferred, deferred_msg);
+    // DISTINCT _dst reads no YIELD program (and the WHERE program only on the VM path)
+    if (fpk.kind == PK_VM || (!default_yield && !(s.distinct && lone_dst))) {
+      dprog.alloc(sizeof(Program) * (yields.size() + 1));
+      c.h2d(dprog.p, &where, sizeof(Program));
+      c.h2d(dprog.as<Program>() + 1, yields.data(), sizeof(Program) * yields.size());
+    }
+    c.timing.edges_scanned += uint64_t(E);
+    rows = std::make_unique<HostRows>();
+    slen.resize(yields.size());
+  }
+
+  // DISTINCT e._dst: mark surviving dsts, compact the whole vertex space (no deg filter).
+  // Bottom-up only when the predicate cannot error (pred_runs_bottom_up).
+  void final_distinct_dst() {
+    const int pk = fpk.kind;
+    const bool bu = pred_bu && want_bu(Eg);
+    DevBuf vids;
+    HostBuf hvids;
+    if (fin_done) {
+      // the speculated final hop ran (spec_replay): its counters, rows and kernel names
+      vids = std::move(spec_vids);
+      hvids = std::move(spec_hvids);
+      nrows = int64_t(fin_h[kSpecRows]);
+      record_bu_hop(fin_h, fin_L, true, nrows);
+    } else if (bu) {
+      FastArgs tfp = fp;
+      if (pk == PK_FAST) tfp.data = es.tr.props[size_t(fpk.col)].data.p;
+      NBG_HIP(hipMemsetAsync(K.d, 0, 8, c.stream));
+      const uint32_t* fb = global_bits(c, bitsA);
+      const BuLaunch L = timed_bu(c.timing.n_hops, [&] {
+        BuLaunch l = launch_bu_lean(c, es, fb, bitsB, nullptr, pk, tfp, pk == PK_FAST ? fpk.col : -1,
+                                    K.d + kCntFinalHop, s.steps > 1);
+        void* vout = vid_block(vids, hvids);
+        launch_bits_vids(c, bitsB, es.tr.n_rows, lo, vout, K.d + kCntList, nullptr);
         NBG_HIP(hipGetLastError());
-        const size_t ib = timing_event(c);
-        c.tpend.push_back(Ctx::PendingTime{ia, ib, c.timing.n_hops, 0});
-        c.tpend.push_back(Ctx::PendingTime{ia, ik, c.timing.n_hops, 1});
-        fetch_counters(c, K.d, 16, K.h);
-        c.timing.expand_launches++;
-        c.timing.bu_steps++;
-        nrows = int64_t(K.h[0]);
-        const int pw = pk == PK_FAST ? tfp.width : 0;
-        const uint64_t kb = bu_first_bytes(K.h + 8, tr.n_rows, 0), hb = kb + bu_rest_bytes(K.h + 8, pw, c.bu_rest_rec);
-        // + the DISTINCT _dst output (k_bits_compact<1>): next bits once, vid_of read + vid written
-        c.timing.expand_bytes += hb + uint64_t(tr.n_rows) / 8 + uint64_t(nrows) * 16;
-        c.timing.hop(1, true, 0.0, K.h + 8, 0.0, kb);
-        c.timing.name_last_hop(c.bu_kernel_name, c.bu_rest_name, "nbg::k_bits_compact<1, 8, 1>");
-      } else {
-        vids.alloc(size_t(c.n_global + 64) * 8);
-        ensure_off();
-        a.F = F;
-        a.nF = nF;
-        a.off = c.ws_off.as<int64_t>();
-        const double ms0 = c.timing.expand_ms;
-        if (E > 0) {
-          launch_expand<EXP_MARK>(c, a, pk, fp, dprog.as<Program>(), env, E);
-          c.timing.expand_bytes += expand_bytes(nF, E, pred_w, EXP_MARK);
-        }
-        const unsigned long long hs[8] = {(unsigned long long)nF, (unsigned long long)E, 0, 0, 0, 0, 0, 0};
-        c.timing.hop(0, true, c.timing.expand_ms - ms0, hs);
-        exchange_marks(c, map);
-        DevBuf lst;
-        lst.alloc(size_t(n_own + 64) * 4);
-        NBG_HIP(hipMemsetAsync(K.d, 0, 16, c.stream));  // keep the eval-error counter (K.d[4])
-        launch_compact(c, map, lo, n_own, row_ptr, nullptr, 0, lst.as<int32_t>(), nullptr, K.d);
-        if (multi) dev_allsum(c, K.d, {4}, K.d + 48);
-        fetch_counters(c, K.d, multi ? 49 : 6, K.h);
-        const int64_t errs = int64_t(K.h[multi ? 48 : 4]);
-        if (errs) throw Error(NBG_E_EVAL, "WHERE evaluation failed");
-        nrows = int64_t(K.h[0]);
-        if (nrows)
-          k_local_to_vid<<<grid_cap(nrows), 256, 0, c.stream>>>(lst.as<int32_t>(), nrows, lo, c.vid_of.as<int64_t>(),
-                                                               vids.as<int64_t>());
-      }
-      h->types.push_back(NBG_T_VID);
-      if (hvids.p) {  // already on the host (host_direct)
-        host_cols[h->dev.size()] = true;
-        h->hpin.push_back(std::move(hvids));
-      }
-      h->dev.push_back(std::move(vids));
+        return l;
+      });
+      fetch_counters(c, K.d, kCntFinalHop + kHopWords, K.h);
+      nrows = int64_t(K.h[kCntList]);
+      record_bu_hop(K.h + kCntFinalHop, L, true, nrows);
     } else {
-      // rows (src, edge) passing WHERE; a lone YIELD _dst (the default) is written directly as
-      // vids by the expansion (no row list, no materialisation pass)
-      ensure_off();
-      a.F = F;
-      a.nF = nF;
-      a.off = c.ws_off.as<int64_t>();
-      const bool dst_only = yields.size() == 1 && yields[0].n == 1 && yields[0].ins[0].op == P_DST;
-      DevBuf fused;
-      int64_t* rows_edge = nullptr;
-      int32_t* rows_src = nullptr;
-      if (dst_only) {
-        fused.alloc(size_t(E + 64) * 8);
-        a.out_vid = fused.as<int64_t>();
-        a.vid_of = c.vid_of.as<int64_t>();
-        a.col_vid = csr.col_vid.as<int64_t>();
-      } else {
-        c.ws_rows.ensure(size_t(E + 64) * 12);
-        rows_edge = c.ws_rows.as<int64_t>();
-        rows_src = reinterpret_cast<int32_t*>(rows_edge + E + 32);
-      }
-      a.rows_edge = rows_edge;
-      a.rows_src = rows_src;
-      a.rows_cnt = K.d + 2;
-      NBG_HIP(hipMemsetAsync(K.d, 0, 48, c.stream));
-      const double ms0 = c.timing.expand_ms;
-      if (E > 0) launch_expand<EXP_ROWS>(c, a, pk, fp, dprog.as<Program>(), env, E);
-      if (multi) dev_allsum(c, K.d, {4}, K.d + 48);
-      fetch_counters(c, K.d, multi ? 49 : 6, K.h);
-      const int64_t errs = int64_t(K.h[multi ? 48 : 4]);
-      if (errs) throw Error(NBG_E_EVAL, "WHERE evaluation failed");
-      const bool direct = dst_only && pk == PK_NONE;  // every edge is a row, written at its index
-      nrows = direct ? E : int64_t(K.h[2]);
-      // the hop's bytes: frontier entries + per edge the col (+ predicate);
-      // per row its 8 B vid write and where the vid comes from: the 8 B dst-vid column read
-      // instead of col (direct rows), else an 8 B vid_of gather behind the col read (a 4 B
-      // (src) + 8 B (edge) row pair without the fused _dst)
-      if (E > 0) {
-        if (direct && csr.col_vid.p)
-          c.timing.expand_bytes += uint64_t(nF) * 28 + uint64_t(E) * 16;
-        else
-          c.timing.expand_bytes += expand_bytes(nF, E, pred_w, EXP_ROWS) + uint64_t(nrows) * (dst_only ? 16 : 12);
-      }
-      const unsigned long long hs[8] = {(unsigned long long)nF, (unsigned long long)E, uint64_t(nrows), 0, 0, 0, 0, 0};
-      c.timing.hop(0, true, c.timing.expand_ms - ms0, hs);
-      YieldArgs ya{};
-      ya.ncols = int32_t(yields.size());
-      for (auto& p : yields) {
-        int32_t t = p.result_type;
-        DevBuf b;
-        if (dst_only) b = std::move(fused);
-        else b.alloc(size_t(nrows + 1) * (t == VT_BOOL ? 1 : 8));
-        const size_t k = h->types.size();
-        if (t == VT_STR) slen[k].alloc(size_t(nrows + 1) * 8);
-        ya.cols[k] = ColOut{b.p, t, slen[k].as<int64_t>()};
-        h->types.push_back(t == VT_DOUBLE ? NBG_T_DOUBLE : t == VT_BOOL ? NBG_T_BOOL : t == VT_STR ? NBG_T_STRING : NBG_T_VID);
-        h->dev.push_back(std::move(b));
-      }
-      if (nrows && !dst_only) {
-        if (default_yield) {
-          k_yield_dst<<<grid_cap(nrows), 256, 0, c.stream>>>(rows_edge, nrows, csr.col.as<int32_t>(),
-                                                             c.vid_of.as<int64_t>(), h->dev[0].as<int64_t>());
-        } else {
-          k_materialize<<<grid_cap(nrows), 256, 0, c.stream>>>(rows_src, rows_edge, nrows, dprog.as<Program>() + 1, ya,
-                                                               env, lo, K.d + 5);
-        }
-        NBG_HIP(hipGetLastError());
-      }
-      if (!dst_only) {  // (the fused _dst rows evaluate nothing: no error count to read)
-        if (multi) dev_allsum(c, K.d, {5}, K.d + 48);
-        fetch_counters(c, K.d, multi ? 49 : 6, K.h);
-        const int64_t yerr = int64_t(K.h[multi ? 48 : 5]);
-        if (yerr) throw Error(NBG_E_EVAL, "YIELD evaluation failed");
-      }
-      if (s.distinct && c.sharded) nrows = shuffle_rows(c, ya, h->dev, nrows);
-      if (s.distinct && nrows) {
-        uint64_t cap = 1024;
-        while (cap < uint64_t(2 * nrows)) cap <<= 1;
-        for (size_t cc = 0; cc < h->dev.size(); cc++) ya.cols[cc].data = h->dev[cc].p;
-        DevBuf table, keep, idx, cnt;
-        table.alloc(cap * 8);
-        NBG_HIP(hipMemsetAsync(table.p, 0xff, cap * 8, c.stream));
-        keep.alloc(size_t(nrows));
-        k_row_dedup<<<grid_cap(nrows), 256, 0, c.stream>>>(ya, nrows, table.as<long long>(), cap - 1, keep.as<uint8_t>());
-        cnt.alloc(8);
-        int64_t kept = 0;
-        for (size_t cc = 0; cc < h->dev.size(); cc++) {
-          DevBuf nb;
-          bool is_bool = ya.cols[cc].type == VT_BOOL;
-          nb.alloc(size_t(nrows + 1) * (is_bool ? 1 : 8));
-          size_t tb = 0;
-          if (is_bool) {
-            NBG_HIP(rocprim::select(nullptr, tb, h->dev[cc].as<uint8_t>(), keep.as<uint8_t>(), nb.as<uint8_t>(),
-                                    cnt.as<uint64_t>(), size_t(nrows), c.stream));
-            c.ws_tmp.ensure(tb);
-            NBG_HIP(rocprim::select(c.ws_tmp.p, tb, h->dev[cc].as<uint8_t>(), keep.as<uint8_t>(), nb.as<uint8_t>(),
-                                    cnt.as<uint64_t>(), size_t(nrows), c.stream));
-          } else {
-            NBG_HIP(rocprim::select(nullptr, tb, h->dev[cc].as<int64_t>(), keep.as<uint8_t>(), nb.as<int64_t>(),
-                                    cnt.as<uint64_t>(), size_t(nrows), c.stream));
-            c.ws_tmp.ensure(tb);
-            NBG_HIP(rocprim::select(c.ws_tmp.p, tb, h->dev[cc].as<int64_t>(), keep.as<uint8_t>(), nb.as<int64_t>(),
-                                    cnt.as<uint64_t>(), size_t(nrows), c.stream));
-          }
-          if (ya.cols[cc].type == VT_STR) {
-            DevBuf nl;
-            nl.alloc(size_t(nrows + 1) * 8);
-            NBG_HIP(rocprim::select(nullptr, tb, slen[cc].as<int64_t>(), keep.as<uint8_t>(), nl.as<int64_t>(),
-                                    cnt.as<uint64_t>(), size_t(nrows), c.stream));
-            c.ws_tmp.ensure(tb);
-            NBG_HIP(rocprim::select(c.ws_tmp.p, tb, slen[cc].as<int64_t>(), keep.as<uint8_t>(), nl.as<int64_t>(),
-                                    cnt.as<uint64_t>(), size_t(nrows), c.stream));
-            slen[cc] = std::move(nl);
-          }
-          uint64_t kc = 0;
-          NBG_HIP(hipMemcpyAsync(&kc, cnt.p, 8, hipMemcpyDeviceToHost, c.stream));
-          host_sync(c);
-          kept = int64_t(kc);
-          h->dev[cc] = std::move(nb);
-        }
-        nrows = kept;
-      }
+      vids.alloc(size_t(c.n_global + 64) * 8);
+      expand_marks(true);
+      DevBuf lst;
+      lst.alloc(size_t(n_own + 64) * 4);
+      NBG_HIP(hipMemsetAsync(K.d, 0, kCntRows * 8, c.stream));  // keep the eval-error counter (kCntWhereErr)
+      launch_compact(c, map, lo, n_own, row_ptr, nullptr, 0, lst.as<int32_t>(), nullptr, K.d);
+      check_eval_errors(kCntWhereErr, "WHERE evaluation failed");
+      nrows = int64_t(K.h[kCntList]);
+      if (nrows)
+        k_local_to_vid<<<grid_cap(nrows), 256, 0, c.stream>>>(lst.as<int32_t>(), nrows, lo, c.vid_of.as<int64_t>(),
+                                                             vids.as<int64_t>());
     }
-  } catch (...) {
-    delete h;
-    throw;
+    HostRows* h = rows.get();
+    h->types.push_back(NBG_T_VID);
+    if (hvids.p) {  // already on the host (host_direct)
+      host_cols[h->dev.size()] = true;
+      h->hpin.push_back(std::move(hvids));
+    }
+    h->dev.push_back(std::move(vids));
   }
-  // ev[1] ends the device time; not waited for here (resolve_total reads it when asked): a
-  // speculated final hop recorded it ahead of its counter fetch, after which nothing was enqueued
-  if (tot_ev && !fin_done) hipEventRecord(c.ev[1], c.stream);
-  c.total_pending = tot_ev;
-  // STRING columns: (address, length) rows -> packed bytes + n+1 offsets
-  const size_t ncols_out = h->types.size();
-  std::vector<int64_t> soff_dev_idx(ncols_out, -1);
-  try {
+
+  // rows (src, edge) passing WHERE; a lone YIELD _dst (the default) is written directly as
+  // vids by the expansion (no row list, no materialisation pass)
+  void final_rows() {
+    HostRows* h = rows.get();
+    const int pk = fpk.kind;
+    ensure_off();
+    frontier_args();
+    DevBuf fused;
+    int64_t* rows_edge = nullptr;
+    int32_t* rows_src = nullptr;
+    if (lone_dst) {
+      fused.alloc(size_t(E + 64) * 8);
+      a.out_vid = fused.as<int64_t>();
+      a.vid_of = c.vid_of.as<int64_t>();
+      a.col_vid = csr.col_vid.as<int64_t>();
+    } else {
+      c.ws_rows.ensure(size_t(E + 64) * 12);
+      rows_edge = c.ws_rows.as<int64_t>();
+      rows_src = reinterpret_cast<int32_t*>(rows_edge + E + 32);
+    }
+    a.rows_edge = rows_edge;
+    a.rows_src = rows_src;
+    a.rows_cnt = K.d + kCntRows;
+    NBG_HIP(hipMemsetAsync(K.d, 0, (kCntYieldErr + 1) * 8, c.stream));
+    const double ms0 = c.timing.expand_ms;
+    if (E > 0) launch_expand<EXP_ROWS>(c, a, pk, fp, dprog.as<Program>(), env, E);
+    check_eval_errors(kCntWhereErr, "WHERE evaluation failed");
+    const bool direct = lone_dst && pk == PK_NONE;  // every edge is a row, written at its index
+    nrows = direct ? E : int64_t(K.h[kCntRows]);
+    // the hop's bytes: frontier entries + per edge the col (+ predicate);
+    // per row its 8 B vid write and where the vid comes from: the 8 B dst-vid column read
+    // instead of col (direct rows), else an 8 B vid_of gather behind the col read (a 4 B
+    // (src) + 8 B (edge) row pair without the fused _dst)
+    if (E > 0) {
+      if (direct && csr.col_vid.p)
+        c.timing.expand_bytes += uint64_t(nF) * 28 + uint64_t(E) * 16;
+      else
+        c.timing.expand_bytes += expand_bytes(nF, E, pred_w(), EXP_ROWS) + uint64_t(nrows) * (lone_dst ? 16 : 12);
+    }
+    record_td_hop(true, c.timing.expand_ms - ms0, nF, E, nrows);
+    YieldArgs ya{};
+    ya.ncols = int32_t(yields.size());
+    for (auto& p : yields) {
+      int32_t t = p.result_type;
+      DevBuf b;
+      if (lone_dst) b = std::move(fused);
+      else b.alloc(size_t(nrows + 1) * (t == VT_BOOL ? 1 : 8));
+      const size_t k = h->types.size();
+      if (t == VT_STR) slen[k].alloc(size_t(nrows + 1) * 8);
+      ya.cols[k] = ColOut{b.p, t, slen[k].as<int64_t>()};
+      h->types.push_back(result_type(t));
+      h->dev.push_back(std::move(b));
+    }
+    if (nrows && !lone_dst) {
+      if (default_yield) {
+        k_yield_dst<<<grid_cap(nrows), 256, 0, c.stream>>>(rows_edge, nrows, csr.col.as<int32_t>(),
+                                                           c.vid_of.as<int64_t>(), h->dev[0].as<int64_t>());
+      } else {
+        k_materialize<<<grid_cap(nrows), 256, 0, c.stream>>>(rows_src, rows_edge, nrows, dprog.as<Program>() + 1, ya,
+                                                             env, lo, K.d + kCntYieldErr);
+      }
+      NBG_HIP(hipGetLastError());
+    }
+    // (the fused _dst rows evaluate nothing: no error count to read)
+    if (!lone_dst) check_eval_errors(kCntYieldErr, "YIELD evaluation failed");
+    if (s.distinct && c.sharded) nrows = shuffle_rows(c, ya, h->dev, nrows);
+    if (s.distinct && nrows) dedup_rows(ya);
+  }
+
+  // DISTINCT over whole rows: a hash table keeps one row of each value, then every column (and
+  // STRING length column) is compacted by the keep flags
+  void dedup_rows(YieldArgs& ya) {
+    HostRows* h = rows.get();
+    uint64_t cap = 1024;
+    while (cap < uint64_t(2 * nrows)) cap <<= 1;
+    for (size_t cc = 0; cc < h->dev.size(); cc++) ya.cols[cc].data = h->dev[cc].p;
+    DevBuf table, keep, idx, cnt;
+    table.alloc(cap * 8);
+    NBG_HIP(hipMemsetAsync(table.p, 0xff, cap * 8, c.stream));
+    keep.alloc(size_t(nrows));
+    k_row_dedup<<<grid_cap(nrows), 256, 0, c.stream>>>(ya, nrows, table.as<long long>(), cap - 1, keep.as<uint8_t>());
+    cnt.alloc(8);
+    int64_t kept = 0;
+    for (size_t cc = 0; cc < h->dev.size(); cc++) {
+      DevBuf nb;
+      bool is_bool = ya.cols[cc].type == VT_BOOL;
+      nb.alloc(size_t(nrows + 1) * (is_bool ? 1 : 8));
+      if (is_bool)
+        select_dev(c, h->dev[cc].as<uint8_t>(), keep.as<uint8_t>(), nb.as<uint8_t>(), cnt.as<uint64_t>(), nrows);
+      else
+        select_dev(c, h->dev[cc].as<int64_t>(), keep.as<uint8_t>(), nb.as<int64_t>(), cnt.as<uint64_t>(), nrows);
+      if (ya.cols[cc].type == VT_STR) {
+        DevBuf nl;
+        nl.alloc(size_t(nrows + 1) * 8);
+        select_dev(c, slen[cc].as<int64_t>(), keep.as<uint8_t>(), nl.as<int64_t>(), cnt.as<uint64_t>(), nrows);
+        slen[cc] = std::move(nl);
+      }
+      uint64_t kc = 0;
+      NBG_HIP(hipMemcpyAsync(&kc, cnt.p, 8, hipMemcpyDeviceToHost, c.stream));
+      host_sync(c);
+      kept = int64_t(kc);
+      h->dev[cc] = std::move(nb);
+    }
+    nrows = kept;
+  }
+
+  // STRING columns: (address, length) rows -> packed bytes + n+1 offsets; then the stream is
+  // drained where the hand-out needs it.  Returns per column the index of its offsets in
+  // rows->dev (-1: not a STRING)
+  std::vector<int64_t> pack_strings() {
+    HostRows* h = rows.get();
+    const size_t ncols_out = h->types.size();
+    std::vector<int64_t> soff_dev_idx(ncols_out, -1);
     for (size_t cc = 0; cc < ncols_out; cc++) {
       if (h->types[cc] != NBG_T_STRING) continue;
       DevBuf off, bytes;
@@ -4057,7 +4136,7 @@ int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
       h->dev.push_back(std::move(off));
     }
     // the result is complete before it is handed out: a host copy waits for its own copies
-    // (below); device columns need the stream drained, which the counter fetch of a speculated
+    // (hand_out); device columns need the stream drained, which the counter fetch of a speculated
     // final hop already saw (nothing was enqueued after it)
     // (STRING columns and very large ones are copied with the blocking hipMemcpy, which does not
     // order behind the engine stream: drained first)
@@ -4069,76 +4148,136 @@ int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
     }
     if (drain && hipStreamQuery(c.stream) != hipSuccess) host_sync(c);
     if (s.keep_on_device || drain) c.host_stage_used = 0;  // the query's input copies have completed
-  } catch (...) {
-    delete h;
-    throw;
+    return soff_dev_idx;
+  }
+
+  // the columns' pointers for the caller: device blocks (keep_on_device), the pinned block the
+  // output kernel wrote (host_direct), or host copies
+  void fill_columns(const std::vector<int64_t>& soff_dev_idx) {
+    HostRows* h = rows.get();
+    const bool on_dev = s.keep_on_device != 0;
+    for (size_t cc = 0; cc < soff_dev_idx.size(); cc++) {
+      if (soff_dev_idx[cc] >= 0) {  // STRING
+        DevBuf& off = h->dev[size_t(soff_dev_idx[cc])];
+        if (on_dev) {
+          h->cols.push_back(h->dev[cc].p);
+          h->str_off.push_back(off.as<int64_t>());
+        } else {
+          h->host_off.emplace_back(size_t(nrows) + 1);
+          NBG_HIP(hipMemcpy(h->host_off.back().data(), off.p, size_t(nrows + 1) * 8, hipMemcpyDeviceToHost));
+          const size_t total = size_t(h->host_off.back()[size_t(nrows)]);
+          h->host.emplace_back(total + 8);
+          if (total) NBG_HIP(hipMemcpy(h->host.back().data(), h->dev[cc].p, total, hipMemcpyDeviceToHost));
+          h->cols.push_back(h->host.back().data());
+          h->str_off.push_back(h->host_off.back().data());
+        }
+        continue;
+      }
+      h->str_off.push_back(nullptr);
+      if (host_cols.count(cc)) {  // written into pinned host memory by the output kernel
+        // the block spans the vertex space (n_global vids): a result far smaller than it is copied
+        // into a right-sized pinned block, so a result the caller keeps pins about its own size (the
+        // large block returns to the context's pinned cache, whose cap bounds what stays held)
+        HostBuf& big = h->hpin.back();
+        const size_t need = size_t(nrows) * 8 + 8;
+        if (need * 4 < big.bytes && need <= (size_t(64) << 20)) {
+          HostBuf small;
+          small.alloc(c.host_pool, need);
+          if (nrows) memcpy(small.p, big.p, size_t(nrows) * 8);
+          big = std::move(small);
+        }
+        h->cols.push_back(h->hpin.back().p);
+      } else if (on_dev) {
+        h->cols.push_back(h->dev[cc].p);
+      } else {
+        size_t w = h->types[cc] == NBG_T_BOOL ? 1 : 8;
+        const size_t bytes = size_t(nrows) * w + 8;
+        if (bytes <= size_t(std::max<int64_t>(0, c.opt("host_pinned_mb", 4096))) << 20) {
+          h->hpin.emplace_back();
+          if (h->hpin.size() == 1) host_pool_cap(c);
+          h->hpin.back().alloc(c.host_pool, bytes);
+          if (nrows)
+            NBG_HIP(hipMemcpyAsync(h->hpin.back().p, h->dev[cc].p, size_t(nrows) * w, hipMemcpyDeviceToHost, c.stream));
+          h->cols.push_back(h->hpin.back().p);
+        } else {  // very large results (RMAT-28's 21 GB of rows): pageable, through the driver
+          h->host.emplace_back(bytes);
+          if (nrows) NBG_HIP(hipMemcpy(h->host.back().data(), h->dev[cc].p, size_t(nrows) * w, hipMemcpyDeviceToHost));
+          h->cols.push_back(h->host.back().data());
+        }
+      }
+    }
+    if (!on_dev) {
+      host_sync(c);  // the pinned copies above (and with them the whole query)
+      c.host_stage_used = 0;
+      h->dev.clear();
+    }
   }
   // hand the columns out (a failed pinned allocation or copy frees the rows and rethrows)
-  bool on_dev = s.keep_on_device != 0;
-  try {
-  for (size_t cc = 0; cc < ncols_out; cc++) {
-    if (soff_dev_idx[cc] >= 0) {  // STRING
-      DevBuf& off = h->dev[size_t(soff_dev_idx[cc])];
-      if (on_dev) {
-        h->cols.push_back(h->dev[cc].p);
-        h->str_off.push_back(off.as<int64_t>());
-      } else {
-        h->host_off.emplace_back(size_t(nrows) + 1);
-        NBG_HIP(hipMemcpy(h->host_off.back().data(), off.p, size_t(nrows + 1) * 8, hipMemcpyDeviceToHost));
-        const size_t total = size_t(h->host_off.back()[size_t(nrows)]);
-        h->host.emplace_back(total + 8);
-        if (total) NBG_HIP(hipMemcpy(h->host.back().data(), h->dev[cc].p, total, hipMemcpyDeviceToHost));
-        h->cols.push_back(h->host.back().data());
-        h->str_off.push_back(h->host_off.back().data());
-      }
-      continue;
+  int32_t hand_out(const std::vector<int64_t>& soff_dev_idx) {
+    try {
+      fill_columns(soff_dev_idx);
+    } catch (...) {
+      // no copy may still target a block freed with the rows (their owner frees them after this)
+      (void)hipStreamSynchronize(c.stream);
+      throw;
     }
-    h->str_off.push_back(nullptr);
-    if (host_cols.count(cc)) {  // written into pinned host memory by the output kernel
-      // the block spans the vertex space (n_global vids): a result far smaller than it is copied
-      // into a right-sized pinned block, so a result the caller keeps pins about its own size (the
-      // large block returns to the context's pinned cache, whose cap bounds what stays held)
-      HostBuf& big = h->hpin.back();
-      const size_t need = size_t(nrows) * 8 + 8;
-      if (need * 4 < big.bytes && need <= (size_t(64) << 20)) {
-        HostBuf small;
-        small.alloc(c.host_pool, need);
-        if (nrows) memcpy(small.p, big.p, size_t(nrows) * 8);
-        big = std::move(small);
-      }
-      h->cols.push_back(h->hpin.back().p);
-    } else if (on_dev) {
-      h->cols.push_back(h->dev[cc].p);
+    fill_rows(out, std::move(rows), nrows, s.keep_on_device != 0);
+    out->edges_scanned = c.timing.edges_scanned;
+    return NBG_OK;
+  }
+};
+
+}  // namespace
+
+int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
+  PoolScope pool_scope(query_pool(c));
+  if (!c.finalized) throw Error(NBG_E_STATE, "snapshot not finalized");
+  if (s.steps < 1) throw Error(NBG_E_INVALID_ARG, "steps must be >= 1");
+  if (s.edge_type <= 0) throw Error(NBG_E_INVALID_ARG, "GO ... REVERSELY is not supported (GoExecutor.cpp:203-205)");
+  auto it = c.edges.find(s.edge_type);
+  if (it == c.edges.end()) throw Error(NBG_E_INVALID_ARG, "edge type not in snapshot");
+  c.timing = Timing{};
+  timing_reset(c);
+  // per-hop event pairs (hop stats); bench.py's timed loop turns them off like a production
+  // caller would, its statistics loop on
+  c.hop_timing = c.opt("hop_timing", 1) != 0;
+  if (c.host_stage_used) host_sync(c);  // a failed query's copies
+  c.host_stage_used = 0;
+  c.total_pending = false;
+  GoQuery q(c, s, it->second, out);
+  if (q.tot_ev) hipEventRecord(c.ev[0], c.stream);
+  q.compile();
+  q.resolve_starts();
+  if (q.nset_global == 0) return q.finish_empty();
+  q.bind_inputs();
+  q.first_degrees();
+  for (int32_t step = 1; step < s.steps; step++) {
+    c.timing.steps_run++;
+    q.clean_shards();  // (the speculated hops' sums were fetched: dense counters from here on)
+    if (q.fast1 && step == 1) {
+      if (!q.hop1_small()) return q.finish_empty();  // every start lacks out-edges
     } else {
-      size_t w = h->types[cc] == NBG_T_BOOL ? 1 : 8;
-      const size_t bytes = size_t(nrows) * w + 8;
-      if (bytes <= size_t(std::max<int64_t>(0, c.opt("host_pinned_mb", 4096))) << 20) {
-        h->hpin.emplace_back();
-        if (h->hpin.size() == 1) host_pool_cap(c);
-        h->hpin.back().alloc(c.host_pool, bytes);
-        if (nrows)
-          NBG_HIP(hipMemcpyAsync(h->hpin.back().p, h->dev[cc].p, size_t(nrows) * w, hipMemcpyDeviceToHost, c.stream));
-        h->cols.push_back(h->hpin.back().p);
-      } else {  // very large results (RMAT-28's 21 GB of rows): pageable, through the driver
-        h->host.emplace_back(bytes);
-        if (nrows) NBG_HIP(hipMemcpy(h->host.back().data(), h->dev[cc].p, size_t(nrows) * w, hipMemcpyDeviceToHost));
-        h->cols.push_back(h->host.back().data());
-      }
+      c.timing.edges_scanned += uint64_t(step == 1 && q.hop1_scanned >= 0 ? q.hop1_scanned : q.E);
+      if (q.Eg == 0) return q.finish_empty();  // every frontier vertex lacks out-edges
+      if (q.want_bu(q.Eg)) q.hop_bottom_up(step);
+      else q.hop_top_down(step);
     }
+    if (q.nset_global == 0) return q.finish_empty();  // onEmptyInputs (GoExecutor.cpp:392-395)
+    step += q.spec_replay();  // the speculated hops that ran behind this one
+    if (q.nset_global == 0) return q.finish_empty();
+    if (q.fin_done) break;
   }
-  if (!on_dev) {
-    host_sync(c);  // the pinned copies above (and with them the whole query)
-    c.host_stage_used = 0;
-    h->dev.clear();
-  }
-  } catch (...) {
-    (void)hipStreamSynchronize(c.stream);  // no copy may still target a block freed here
-    delete h;
-    throw;
-  }
-  fill_rows(out, h, nrows, on_dev);
-  out->edges_scanned = c.timing.edges_scanned;
-  return NBG_OK;
+  // ---- final step ----
+  c.timing.steps_run++;
+  if (!q.fin_done) q.clean_shards();
+  q.begin_final();
+  if (s.distinct && q.lone_dst) q.final_distinct_dst();
+  else q.final_rows();
+  // ev[1] ends the device time; not waited for here (resolve_total reads it when asked): a
+  // speculated final hop recorded it ahead of its counter fetch, after which nothing was enqueued
+  if (q.tot_ev && !q.fin_done) hipEventRecord(c.ev[1], c.stream);
+  c.total_pending = q.tot_ev;
+  return q.hand_out(q.pack_strings());
 }
 
 void timing_reset(Ctx& c) {
@@ -4457,9 +4596,7 @@ void fetch_vertex_tags(Ctx& c, HostRows* h, const std::vector<int32_t>& vparts, 
       const bool foreign = hs[size_t(i)] == 2 && rp == hp[size_t(i)];
       pres[size_t(i)] = own || foreign;
     }
-    h->vertex_types.push_back(pc.type == NBG_T_FLOAT                               ? NBG_T_DOUBLE
-                              : (pc.type == NBG_T_VID || pc.type == NBG_T_TIMESTAMP) ? NBG_T_INT
-                                                                                     : pc.type);
+    h->vertex_types.push_back(column_result_type(pc.type));
     h->vertex_present.push_back(pres);
     if (is_str) {
       std::vector<int64_t> offs(size_t(nv) + 1, 0);
@@ -4494,9 +4631,9 @@ int32_t get_bound_run(Ctx& c, int32_t et, const int32_t* parts, const int64_t* v
                       size_t flen, const nbg_prop_def* cols, size_t ncols, nbg_rows* out, const int32_t* stats) {
   PoolScope pool_scope(query_pool(c));
   if (!c.finalized) throw Error(NBG_E_STATE, "snapshot not finalized");
-  auto* h = new HostRows();
+  auto h = std::make_unique<HostRows>();
   auto finish = [&](int64_t nrows) {
-    fill_rows(out, h, nrows, false);
+    fill_rows(out, std::move(h), nrows, false);
     return NBG_OK;
   };
   // request-level validation -> every part of the request fails (QueryBaseProcessor.inl:470-477)
@@ -4537,10 +4674,7 @@ int32_t get_bound_run(Ctx& c, int32_t et, const int32_t* parts, const int64_t* v
       if (fi == tit->second.fields.size()) return fail_all(NBG_E_IMPROPER_DATA_TYPE);
       if (stats) {  // validOperation over the tag prop's type (QueryBaseProcessor.inl:62-64)
         const int32_t st = stats[i];
-        if (st < 1 || st > 3) {
-          delete h;
-          throw Error(NBG_E_INVALID_ARG, "stat type must be SUM 1, COUNT 2 or AVG 3");
-        }
+        if (st < 1 || st > 3) throw Error(NBG_E_INVALID_ARG, "stat type must be SUM 1, COUNT 2 or AVG 3");
         const int32_t t = tit->second.fields[fi].type;
         if (st != 2 && (t == NBG_T_BOOL || t == NBG_T_STRING)) return fail_all(NBG_E_IMPROPER_DATA_TYPE);
         sorder.emplace_back(1, int(treq.size()));
@@ -4565,43 +4699,30 @@ int32_t get_bound_run(Ctx& c, int32_t et, const int32_t* parts, const int64_t* v
       b.kind = 0;
       b.prop = idx;
       int32_t t = es.fields[size_t(idx)].type;
-      b.type = (t == NBG_T_FLOAT) ? NBG_T_DOUBLE : (t == NBG_T_VID || t == NBG_T_TIMESTAMP) ? NBG_T_INT : t;
+      b.type = column_result_type(t);
     } else {
       continue;  // "InBound has none props, skip it!"
     }
     if (stats) {  // validOperation (QueryBaseProcessor.inl:18-35): SUM / AVG need a numeric column
       b.stat = stats[i];
-      if (b.stat < 1 || b.stat > 3) {
-        delete h;
-        throw Error(NBG_E_INVALID_ARG, "stat type must be SUM 1, COUNT 2 or AVG 3");
-      }
+      if (b.stat < 1 || b.stat > 3) throw Error(NBG_E_INVALID_ARG, "stat type must be SUM 1, COUNT 2 or AVG 3");
       if (b.stat != 2 && (b.type == NBG_T_BOOL || b.type == NBG_T_STRING)) return fail_all(NBG_E_IMPROPER_DATA_TYPE);
     }
-    if (bc.n >= kMaxBoundCols) {
-      delete h;
-      throw Error(NBG_E_UNSUPPORTED, "too many return columns");
-    }
+    if (bc.n >= kMaxBoundCols) throw Error(NBG_E_UNSUPPORTED, "too many return columns");
     if (stats) sorder.emplace_back(0, bc.n);
     bc.c[bc.n++] = b;
   }
   Program fprog{};
-  int pk = PK_NONE;
-  FastArgs fp{};
+  FastPred fpk{};
   if (flen) {
     std::string msg;
     int32_t rc = compile_expr(filter, flen, es.fields, false, !in_bound, &fprog, &msg, &c.tag_refs);
-    if (rc == NBG_E_UNSUPPORTED) {
-      delete h;
-      throw Error(rc, "filter: " + msg);
-    }
+    if (rc == NBG_E_UNSUPPORTED) throw Error(rc, "filter: " + msg);
     if (rc != NBG_OK) return fail_all(NBG_E_INVALID_FILTER);
-    FastPred f = classify_pred(fprog, es.fields);
-    pk = f.kind;
-    if (pk == PK_FAST) {
-      const PropCol& pc = csr.props[size_t(f.col)];
-      fp = FastArgs{pc.data.p, pc.present.as<uint8_t>(), pc.width, f.op, f.k};
-    }
+    fpk = classify_pred(fprog, es.fields);
   }
+  const int pk = fpk.kind;
+  const FastArgs fp = fast_args(csr, fpk);
   int64_t N = int64_t(n);
   const int64_t lo = c.owned_lo(), hi = c.owned_hi();
   // parts not held by this rank -> E_PART_NOT_FOUND (NebulaStore::engine, BaseProcessor.inl:14-27)
@@ -4681,11 +4802,8 @@ int32_t get_bound_run(Ctx& c, int32_t et, const int32_t* parts, const int64_t* v
     c.timing.expand_bytes += expand_bytes(nF, E, pk == PK_FAST ? fp.width : 0, EXP_FLAGS);
     slots.alloc(size_t(E + 1) * 8);
     cnt.alloc(8);
-    size_t tb = 0;
-    auto first = rocprim::counting_iterator<int64_t>(0);
-    NBG_HIP(rocprim::select(nullptr, tb, first, flags.as<uint8_t>(), slots.as<int64_t>(), cnt.as<uint64_t>(), size_t(E), c.stream));
-    c.ws_tmp.ensure(tb);
-    NBG_HIP(rocprim::select(c.ws_tmp.p, tb, first, flags.as<uint8_t>(), slots.as<int64_t>(), cnt.as<uint64_t>(), size_t(E), c.stream));
+    select_dev(c, rocprim::counting_iterator<int64_t>(0), flags.as<uint8_t>(), slots.as<int64_t>(),
+               cnt.as<uint64_t>(), E);
     uint64_t hm = 0;
     NBG_HIP(hipMemcpyAsync(&hm, cnt.p, 8, hipMemcpyDeviceToHost, c.stream));
     NBG_HIP(hipStreamSynchronize(c.stream));
@@ -4716,9 +4834,8 @@ int32_t get_bound_run(Ctx& c, int32_t et, const int32_t* parts, const int64_t* v
     oenv.props = oprops;
     FastArgs ofp{};
     if (pk == PK_FAST) {
-      const FastPred f = classify_pred(fprog, es.fields);
-      const PropCol& oc = csr.ov_props[size_t(f.col)];
-      ofp = FastArgs{oc.data.p, oc.present.as<uint8_t>(), 8, f.op, f.k};
+      const PropCol& oc = csr.ov_props[size_t(fpk.col)];
+      ofp = FastArgs{oc.data.p, oc.present.as<uint8_t>(), 8, fpk.op, fpk.k};
     }
     DevBuf xo, xg, cx;
     xo.alloc(size_t(nF) * 8);
@@ -4818,10 +4935,8 @@ int32_t get_bound_run(Ctx& c, int32_t et, const int32_t* parts, const int64_t* v
         if (!vis) continue;
         tcnt[t]++;
         if (ty == NBG_T_DOUBLE || ty == NBG_T_FLOAT) {
-          if (tstat[t] != 2) {
-            delete h;
+          if (tstat[t] != 2)
             throw Error(NBG_E_UNSUPPORTED, "SUM/AVG over a double prop (the reference's int64 sum throws bad_get)");
-          }
         } else if (ty != NBG_T_BOOL && ty != NBG_T_STRING) {
           tsum[t] = int64_t(uint64_t(tsum[t]) + uint64_t(tval[t][size_t(i)]));
         }
@@ -4850,10 +4965,8 @@ int32_t get_bound_run(Ctx& c, int32_t et, const int32_t* parts, const int64_t* v
       const BoundCol& b = bc.c[i];
       const int64_t sum = int64_t(ha[size_t(2 * i)]);
       const int64_t cnt = int64_t(ha[size_t(2 * i + 1)]);
-      if (b.stat != 2 && b.type == NBG_T_DOUBLE && cnt > 0) {
-        delete h;
+      if (b.stat != 2 && b.type == NBG_T_DOUBLE && cnt > 0)
         throw Error(NBG_E_UNSUPPORTED, "SUM/AVG over a double prop (the reference's int64 sum throws bad_get)");
-      }
       h->types.push_back(b.stat == 3 ? NBG_T_DOUBLE : NBG_T_INT);
       h->host.emplace_back(8);
       if (b.stat == 3) {
@@ -4950,10 +5063,10 @@ int32_t get_bound_run(Ctx& c, int32_t et, const int32_t* parts, const int64_t* v
       if (k != last) vparts.push_back(parts[centry[size_t(k)]]);
       last = k;
     }
-    fetch_vertex_tags(c, h, vparts, [&](size_t t) { return std::make_pair(treq[t].ts, treq[t].field); },
+    fetch_vertex_tags(c, h.get(), vparts, [&](size_t t) { return std::make_pair(treq[t].ts, treq[t].field); },
                       treq.size());
   }
-  fill_rows(out, h, m, false);
+  fill_rows(out, std::move(h), m, false);
   out->edges_scanned = uint64_t(E);
   return NBG_OK;
 }

@@ -715,3 +715,98 @@ def test_atomic_hop_sums_match(rmat12, bu_div):
     finally:
         sp.unset_option("bu_atomic_sums")
         sp.set_option("bu_div", 4)
+
+
+# ------------------------------------------------------------------------------------------
+# RMAT-10: results kept on the device, and more starts than the one-launch start frontier takes
+# ------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def rmat10():
+    sp = GraphSpace(64)
+    sp.set_edge_schema(FOLLOW, [("weight", O.INT)])
+    sp.gen_rmat(10, 16, SEED, FOLLOW)
+    sp.finalize()
+    st = oracle_rmat(10)
+    yield sp, st
+    sp.close()
+
+
+def device_rows(sp):
+    """the query sp.go(keep_on_device=True) just ran, issued again from its prepared spec with the
+    rows held: their first column copied from the device (GraphSpace.go itself hands the device
+    blocks back before it returns)"""
+    import ctypes as C
+
+    from nebula_amd import _lib
+    rows = _lib.Rows()
+    sp._check(sp.L.nbg_go(sp.h, C.byref(sp._last_spec[1]), C.byref(rows)))
+    try:
+        assert rows.on_device == 1 and rows.n_cols == 1
+        copy = sp.L.hipMemcpy
+        copy.restype, copy.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        col = np.empty(int(rows.n_rows), dtype=np.int64)
+        if rows.n_rows:
+            assert copy(col.ctypes.data, rows.cols[0], col.nbytes, 2) == 0  # 2: hipMemcpyDeviceToHost
+        return col, int(rows.edges_scanned)
+    finally:
+        sp.L.nbg_rows_free(C.byref(rows))
+
+
+def test_rmat10_keep_on_device(rmat10):
+    """keep_on_device: the result columns stay in device memory (the DISTINCT _dst block of the
+    speculated final hop, and the plain rows of a top-down final hop); same rows and edge counts
+    as the oracle, and as the host copy of the same query"""
+    sp, st = rmat10
+    starts = seeds_from(10, 16)
+    w = X.AliasProp("follow", "weight") > 499
+    y = [X.EdgeDst("follow")]
+    r = st.go(starts, 3, FOLLOW, where=w.encode(), yields=[y[0].encode()], distinct=True)
+    g = sp.go(starts, 3, FOLLOW, where=w, yields=y, distinct=True, keep_on_device=True)
+    assert g.on_device and g.n_rows == r.nrows and g.columns == [None] and len(g.device_ptrs) == 1
+    col, scanned = device_rows(sp)
+    assert np.array_equal(np.sort(col), np.sort(r.int_col(0))) and scanned == r.edges_scanned
+    assert sp.last_timing()["spec_hops"] >= 1
+    h = sp.go(starts, 3, FOLLOW, where=w, yields=y, distinct=True)
+    assert np.array_equal(np.sort(h.columns[0]), np.sort(col))
+    r = st.go(starts, 2, FOLLOW)
+    g = sp.go(starts, 2, FOLLOW, keep_on_device=True)
+    assert g.on_device and g.n_rows == r.nrows
+    col, scanned = device_rows(sp)
+    assert np.array_equal(np.sort(col), np.sort(r.int_col(0))) and scanned == r.edges_scanned
+
+
+@pytest.mark.parametrize("force", [0, 1, -1])
+def test_rmat10_one_step_distinct_dst(rmat10, force):
+    """1 step DISTINCT _dst on one rank: the start frontier deduplicated through the bitmap, then
+    the final hop alone, top-down or bottom-up"""
+    sp, st = rmat10
+    starts = seeds_from(10, 16)
+    starts = starts + starts[:4]
+    y = [X.EdgeDst("follow")]
+    sp.set_option("bu_force", force)
+    try:
+        g = sp.go(starts, 1, FOLLOW, yields=y, distinct=True)
+        r = st.go(starts, 1, FOLLOW, yields=[y[0].encode()], distinct=True)
+        assert np.array_equal(np.sort(g.columns[0]), np.sort(r.int_col(0)))
+        assert g.edges_scanned == r.edges_scanned
+        if force:
+            assert sp.last_timing()["bu_steps"] == (1 if force == 1 else 0)
+    finally:
+        sp.unset_option("bu_force")
+
+
+def test_rmat10_5000_starts(rmat10):
+    """5000 starts, past what the one-launch start frontier (k_starts_small) takes, with the
+    default direction rule: 3 steps of plain rows and the DISTINCT _dst query against the oracle"""
+    sp, st = rmat10
+    starts = seeds_from(10, 5000, seed=5)
+    g = sp.go(starts, 3, FOLLOW)
+    r = st.go(starts, 3, FOLLOW)
+    assert np.array_equal(np.sort(g.columns[0]), np.sort(r.int_col(0)))
+    assert g.edges_scanned == r.edges_scanned
+    w = X.AliasProp("follow", "weight") > 499
+    y = [X.EdgeDst("follow")]
+    g = sp.go(starts, 3, FOLLOW, where=w, yields=y, distinct=True)
+    r = st.go(starts, 3, FOLLOW, where=w.encode(), yields=[y[0].encode()], distinct=True)
+    assert np.array_equal(np.sort(g.columns[0]), np.sort(r.int_col(0)))
+    assert g.edges_scanned == r.edges_scanned
