@@ -87,7 +87,7 @@ int32_t nbg_comm_info(nbg_ctx* ctx, int32_t* ranks, int32_t* transport);
  * nbg_hop_stat, nbg_snapshot_info, nbg_go_spec, nbg_rows) change layout between versions: an
  * integration compares nbg_abi_version() with the NBG_ABI_VERSION it was built against and
  * refuses to run on a mismatch (INTEGRATION.md "ABI versioning").                          */
-#define NBG_ABI_VERSION 6
+#define NBG_ABI_VERSION 7
 int32_t nbg_abi_version(void);
 /* sizeof of the caller-allocated structs as the library was built: 0 nbg_timing, 1
  * nbg_hop_stat, 2 nbg_snapshot_info, 3 nbg_go_spec, 4 nbg_rows, 5 nbg_prop_def; -1 otherwise */
@@ -233,7 +233,20 @@ int32_t nbg_bound_stats(nbg_ctx* ctx, int32_t edge_type, const int32_t* parts, c
  * 334-431, 585-782) with one device-resident call.  starts: literal or piped vids (duplicates
  * kept unless distinct, GoExecutor.cpp:98-104).  where/yields: Expression::encode bytes as the
  * graphd AST would encode them.  n_yields = 0 means the default YIELD e._dst AS id.
- * With world_size > 1 every rank passes the same spec; rows come back sharded by owner.     */
+ * With world_size > 1 every rank passes the same spec; rows come back sharded by owner.
+ *
+ * GO UPTO N STEPS (upto = 1; the reference parses it, parser.yy:455, and refuses to run it,
+ * GoExecutor.cpp:121-123; semantics owned by this build, DESIGN.md divergence 7): the rows of
+ * GO 1 STEPS, GO 2 STEPS, ... GO N STEPS with the same starts, edge type, WHERE and YIELD,
+ * concatenated (row order unspecified); distinct = 1 removes duplicates over the whole
+ * concatenation.  A frontier that becomes empty at step k ends the query with the rows of steps
+ * 1 .. k-1 (not the empty result of plain GO N STEPS).  A WHERE / YIELD evaluation error at any
+ * step fails the query (NBG_E_EVAL).  upto = 1 with steps = 1 is GO 1 STEPS.  $- / $var
+ * properties in WHERE or YIELD are not supported under UPTO (NBG_E_UNSUPPORTED; piped starts
+ * without input properties work); upto outside {0, 1} is NBG_E_INVALID_ARG.
+ * edges_scanned: without distinct the (step, adjacency entry) pairs examined; with distinct the
+ * engine runs a visited-pruned BFS and one final step: sum over k < N of outdeg(B_k), B_k the
+ * vertices first reached at hop k-1 (B_1 the distinct starts), plus outdeg(union of the B_k).  */
 typedef struct {
   int32_t edge_type;
   int32_t steps;
@@ -260,6 +273,7 @@ typedef struct {
   const int32_t* input_types;
   const void* const* input_cols;
   const int64_t* const* input_str_offsets;
+  int32_t upto;           /* 1: GO UPTO `steps` STEPS (ABI 7; last, so zeroed specs stay valid) */
 } nbg_go_spec;
 int32_t nbg_go(nbg_ctx* ctx, const nbg_go_spec* spec, nbg_rows* out);
 
@@ -281,6 +295,9 @@ int32_t nbg_shortest_path(nbg_ctx* ctx, int32_t edge_type, const int64_t* src,
  * bottom-up {found, next-hop out-degree sum, slab words read, rows scanned past the slab,
  * entries read past the slab, predicate values read past the slab, first-pass frontier probes
  * answered by L2, first-pass probes answered from the LDS hub copy}.
+ * A hop of a GO UPTO ... DISTINCT's pruned BFS (final_hop = 0; kernels names nbg::k_upto_claim,
+ * mode 0, or nbg::k_upto_bu, mode 1): c[] = {vertices first reached, their out-degree sum, size
+ * of the level expanded, adjacency entries read, 0, 0, 0, 0}; its final step records as above.
  * nbg_shortest_path records one entry per launch instead: mode 2 = BFS expansion, 3 = meet
  * probe, 4 = sweep; c[] = {tuples, adjacency entries, claims, meets so far, iteration,
  * active pairs, 0, 0}; 5 = walk scan (device-driven batches), c[] = {chunks, adjacency

@@ -22,7 +22,7 @@ ERRORS = {
 }
 T_BOOL, T_INT, T_VID, T_FLOAT, T_DOUBLE, T_STRING, T_TIMESTAMP = 1, 2, 3, 4, 5, 6, 21
 OWNER_SOURCE, OWNER_DEST, OWNER_EDGE = 1, 2, 3
-ABI_VERSION = 6  # NBG_ABI_VERSION of include/nebula_amd.h
+ABI_VERSION = 7  # NBG_ABI_VERSION of include/nebula_amd.h
 
 # every symbol the header declares (tests/test_capi.py checks the .so exports them all)
 EXPORTS = [
@@ -75,7 +75,7 @@ class GoSpec(C.Structure):
                 ("n_yields", C.c_size_t), ("distinct", C.c_int32), ("keep_on_device", C.c_int32),
                 ("n_inputs", C.c_size_t), ("input_names", C.POINTER(C.c_char_p)),
                 ("input_types", C.POINTER(C.c_int32)), ("input_cols", C.POINTER(C.c_void_p)),
-                ("input_str_offsets", C.POINTER(C.c_void_p))]
+                ("input_str_offsets", C.POINTER(C.c_void_p)), ("upto", C.c_int32)]
 
 
 class HopStat(C.Structure):

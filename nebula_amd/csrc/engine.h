@@ -548,6 +548,7 @@ struct Ctx {
   DevBuf ws_starts;
   DevBuf ws_partials;  // per-block partial sums of the aggregated kernels
   DevBuf ws_pend;      // deferred bottom-up rows: pending bits + compacted list
+  DevBuf ws_vis;       // GO UPTO DISTINCT: visited bitmap, then the union-of-levels bitmap (owned rows)
   // FIND SHORTEST PATH distance bytes [side][pair][owned row], kept 0xFF between calls, and
   // its tuple lists (kept across calls; allocated outside the query pool)
   DevBuf sp_dist[2];

@@ -725,6 +725,7 @@ enum CounterWord : int {
   kCntStartsN = 40,   // k_starts_small: the start list's length
   kCntStartsE = 41,   // ... and its out-degree sum
   kCntGlobal = 48,    // [48, 52): counters summed over ranks on the device (dev_allsum's output)
+  kCntUpto = 56,      // [56, 60): the sums of a GO UPTO hop (k_upto_claim / k_upto_bu)
   kSpecBase = 64,     // the first speculated hop's block
 };
 // a speculated hop's block: kSpecWords words at kSpecBase + kSpecWords * (position in the chain)
@@ -2100,6 +2101,136 @@ __global__ __launch_bounds__(256) void k_or_segments_bits(const uint32_t* __rest
   }
   block_add_sums(acc, 3, lds, sums);
 }
+
+// ---- GO UPTO N STEPS, DISTINCT: the hop kernels of the visited-pruned BFS (GoQuery::run_upto) ----
+// State over the rank's owned rows, 64 rows a word: vis (vertices reached so far, the starts
+// included), uni (of them those with out-edges: the union of the BFS levels B_k, the frontier of
+// the one final step) and next (B_k+1: the rows first reached by this hop that have out-edges).
+// One wave owns 64 consecutive rows in both kernels: it builds each word with a 64-bit ballot and
+// lane 0 stores it, so no bitmap word needs an atomic and none is read by one workgroup and
+// written by another inside a launch; the hops see each other's words through the stream order of
+// their launches only.  sums (zeroed by the caller with their shards; one agent-scope add per
+// block and word into shard block % shards, block_add_sums):
+// [0] rows first reached, [1] their out-degree sum, [2] those of them with out-edges (next's
+// population), [3] adjacency entries read (k_upto_bu).
+//
+// k_upto_claim, behind a top-down hop: mark = the owned slice of the byte map the expansion (and
+// the mark exchange) wrote.  new = mark & ~vis; vis |= new; the marks are cleared.  Rows at or past
+// n_read carry no mark (no in-edge: the class-ordered numbering puts them last) and are not read.
+// list (optional): next as a list of local rows too, list_n its length.
+__global__ __launch_bounds__(256) void k_upto_claim(uint8_t* __restrict__ mark, int64_t n, int64_t n_read,
+                                                    const uint32_t* __restrict__ odeg,
+                                                    unsigned long long* __restrict__ vis,
+                                                    unsigned long long* __restrict__ uni,
+                                                    unsigned long long* __restrict__ next, int32_t* __restrict__ list,
+                                                    unsigned long long* list_n, unsigned long long* sums,
+                                                    int shards) {
+  __shared__ unsigned long long lds[kSlots * 16];
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
+  const int64_t nwords = (n + 63) / 64;
+  unsigned long long acc[3] = {0, 0, 0};
+  // (four words a step with their mark loads issued together measured the same: 0.1037 against
+  // 0.1016 ms for the hop at RMAT-26)
+  for (int64_t w = wave; w < nwords; w += nwaves) {  // (wave-uniform)
+    const int64_t row = w * 64 + lane;
+    const bool marked = row < n && row < n_read && mark[row] != 0;
+    const unsigned long long mk = __ballot(marked);
+    unsigned long long keep = 0;
+    if (mk) {
+      const unsigned long long v = vis[w];
+      const unsigned long long fresh = mk & ~v;
+      const bool mine = (fresh >> lane) & 1ull;
+      const uint32_t d = mine ? odeg[row] : 0u;
+      keep = __ballot(mine && d > 0);
+      if (marked) mark[row] = 0;
+      if (lane == 0 && fresh) vis[w] = v | fresh;
+      if (lane == 0 && keep) uni[w] |= keep;
+      acc[0] += mine ? 1u : 0u;
+      acc[1] += d;
+      acc[2] += mine && d > 0 ? 1u : 0u;
+      if (list && keep) {
+        const int64_t s = wave_append(list_n, mine && d > 0);
+        if (s >= 0) list[s] = int32_t(row);
+      }
+    }
+    if (lane == 0) next[w] = keep;
+  }
+  block_add_sums(acc, 3, lds, sums, shards);
+}
+
+// k_upto_bu, a bottom-up hop over the plain transposed CSR (trp / tcol: row = owned dst, entries
+// = global src index): only rows not yet in vis are scanned, and a row stops at its first
+// in-neighbour in the frontier bitmap fb (over the whole gidx space, fb_bits bits).  A fixed-depth
+// GO cannot skip reached rows (it must reach them again), which is why its kernels do not fit.
+// Each lane scans its row's first kUptoLane entries alone; rows still open after that are scanned
+// by the whole wave, 64 entries a step, so one long unreached row is not one lane's serial loop.
+// Rows at or past n_scan have no in-edge: their next words are written as zero without a read.
+constexpr int kUptoLane = 4;
+__global__ __launch_bounds__(256) void k_upto_bu(const int64_t* __restrict__ trp, const int32_t* __restrict__ tcol,
+                                                 int64_t n, int64_t n_scan, const uint32_t* __restrict__ fb,
+                                                 int64_t fb_bits, const uint32_t* __restrict__ odeg,
+                                                 unsigned long long* __restrict__ vis,
+                                                 unsigned long long* __restrict__ uni,
+                                                 unsigned long long* __restrict__ next, unsigned long long* sums,
+                                                 int shards) {
+  __shared__ unsigned long long lds[kSlots * 16];
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
+  const int64_t nwords = (n + 63) / 64;
+  auto in_front = [&](int32_t s) {
+    return s >= 0 && int64_t(s) < fb_bits && ((fb[uint32_t(s) >> 5] >> (uint32_t(s) & 31u)) & 1u) != 0u;
+  };
+  unsigned long long acc[4] = {0, 0, 0, 0};
+  for (int64_t w = wave; w < nwords; w += nwaves) {  // (wave-uniform)
+    const int64_t row = w * 64 + lane;
+    unsigned long long keep = 0;
+    if (w * 64 < n_scan) {
+      const unsigned long long v = vis[w];
+      const bool open = row < n && row < n_scan && !((v >> lane) & 1ull);
+      int64_t b = 0, e = 0;
+      if (open) b = trp[row], e = trp[row + 1];
+      // entry by entry: the rows are ordered hub-first, so the first entry is most often the hit,
+      // and the kernel is bound by the entries it reads (loading a lane's four entries together
+      // read 2.5x the entries and took 0.366 -> 0.465 ms at RMAT-26, profiles/upto_compare.md)
+      bool found = false;
+      for (int i = 0; i < kUptoLane; i++) {
+        if (found || b + i >= e) continue;
+        found = in_front(tcol[b + i]);
+        acc[3]++;
+      }
+      unsigned long long pend = __ballot(!found && b + kUptoLane < e);
+      while (pend) {
+        const int l = __ffsll((long long)pend) - 1;
+        pend &= pend - 1;
+        const int64_t rb = __shfl(b, l) + kUptoLane, re = __shfl(e, l);
+        bool hit = false;
+        for (int64_t p = rb; p < re && !hit; p += 64) {
+          const int64_t i = p + lane;
+          bool h = false;
+          if (i < re) {
+            h = in_front(tcol[i]);
+            acc[3]++;
+          }
+          hit = __ballot(h) != 0ull;
+        }
+        if (lane == l) found = hit;
+      }
+      const unsigned long long fresh = __ballot(found);
+      const uint32_t d = found ? odeg[row] : 0u;
+      keep = __ballot(found && d > 0);
+      if (lane == 0 && fresh) vis[w] = v | fresh;
+      if (lane == 0 && keep) uni[w] |= keep;
+      acc[0] += found ? 1u : 0u;
+      acc[1] += d;
+      acc[2] += found && d > 0 ? 1u : 0u;
+    }
+    if (lane == 0) next[w] = keep;
+  }
+  block_add_sums(acc, 4, lds, sums, shards);
+}
 // DISTINCT over rows with several ranks: rows are shuffled to rank hash(row) % G first
 __global__ void k_flag_dest(const uint32_t* dest, int64_t n, uint32_t p, uint8_t* flag) {
   for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x)
@@ -3168,6 +3299,8 @@ struct GoQuery {
   std::vector<Program> yields;
   std::vector<Field> in_fields;  // $- / $var input table columns
   const bool has_where, default_yield;
+  // GO UPTO N STEPS (nbg_go_spec::upto with steps > 1; UPTO 1 STEPS is GO 1 STEPS): run_upto
+  const bool upto;
   // compile errors are deferred to the final step, as the reference only reports them when the
   // final getNeighbors request is actually sent
   int32_t deferred = NBG_OK;
@@ -3291,7 +3424,7 @@ struct GoQuery {
 
   GoQuery(Ctx& c_, const nbg_go_spec& s_, EdgeSpace& es_, nbg_rows* out_)
       : c(c_), s(s_), es(es_), csr(es_.out), out(out_), tot_ev(c_.hop_timing), has_where(s_.where_len > 0),
-        default_yield(s_.n_yields == 0) {}
+        default_yield(s_.n_yields == 0), upto(s_.upto == 1 && s_.steps > 1) {}
 
   // WHERE / YIELD programs, the input table's columns (validated here, uploaded once the starts
   // are resolved) and the predicate's class
@@ -3338,6 +3471,8 @@ struct GoQuery {
     for (auto& p : yields)
       for (int i = 0; i < p.n; i++) uses_input |= p.ins[i].op == P_INPUT;
     lone_dst = is_lone_dst(yields);
+    if (upto && uses_input)
+      throw Error(NBG_E_UNSUPPORTED, "GO UPTO with $- / $var properties in WHERE or YIELD is not supported");
     if (deferred == NBG_OK) {
       fpk = has_where ? classify_pred(where, es.fields) : FastPred{};
       fp = fast_args(csr, fpk);
@@ -3381,7 +3516,7 @@ struct GoQuery {
     const bool td1_certain =
         !bu_ok || bu_force < 0 || (bu_force == 0 && deg_bound < es.out_nnz_global / bu_div);
     fast1 = ns > 0 && ns <= kSmallStarts && s.steps >= 2 && td1_certain && !(uses_input && s.steps > 1) &&
-            c.opt("starts_small", 1) != 0;
+            c.opt("starts_small", 1) != 0 && !upto;
     multi = c.sharded;
     ks = multi ? 1 : int(std::min<int64_t>(std::max<int64_t>(c.opt("sum_shards", kSumShards), 1), kSumShards));
     // the small-start path's one block reads the starts from coherent pinned host memory (the
@@ -3538,7 +3673,7 @@ struct GoQuery {
       env.iprops = in_tab.as<PropDev>();
     }
     host_direct = !s.keep_on_device && c.opt("host_direct", 1) != 0;
-    spec_ok = bu_ok && !multi_root && bu_force >= 0 && c.opt("bu_spec", 1) != 0;
+    spec_ok = bu_ok && !multi_root && bu_force >= 0 && c.opt("bu_spec", 1) != 0 && !upto;
     spec_thr = bu_force > 0 ? 1ull : (unsigned long long)std::max<int64_t>(1, es.out_nnz_global / bu_div);
   }
 
@@ -3943,7 +4078,7 @@ struct GoQuery {
     }
     if (deferred != NBG_OK) throw Error(deferred, deferred_msg);
     // DISTINCT _dst reads no YIELD program (and the WHERE program only on the VM path)
-    if (fpk.kind == PK_VM || (!default_yield && !(s.distinct && lone_dst))) {
+    if (!dprog.p && (fpk.kind == PK_VM || (!default_yield && !(s.distinct && lone_dst)))) {
       dprog.alloc(sizeof(Program) * (yields.size() + 1));
       c.h2d(dprog.p, &where, sizeof(Program));
       c.h2d(dprog.as<Program>() + 1, yields.data(), sizeof(Program) * yields.size());
@@ -3973,7 +4108,7 @@ struct GoQuery {
       const uint32_t* fb = global_bits(c, bitsA);
       const BuLaunch L = timed_bu(c.timing.n_hops, [&] {
         BuLaunch l = launch_bu_lean(c, es, fb, bitsB, nullptr, pk, tfp, pk == PK_FAST ? fpk.col : -1,
-                                    K.d + kCntFinalHop, s.steps > 1);
+                                    K.d + kCntFinalHop, s.steps > 1 && !upto);
         void* vout = vid_block(vids, hvids);
         launch_bits_vids(c, bitsB, es.tr.n_rows, lo, vout, K.d + kCntList, nullptr);
         NBG_HIP(hipGetLastError());
@@ -4225,6 +4360,198 @@ struct GoQuery {
     out->edges_scanned = c.timing.edges_scanned;
     return NBG_OK;
   }
+
+  // ---- GO UPTO N STEPS (DESIGN.md divergence 7): the rows of GO 1 .. N STEPS together ----
+  // Host-driven, no speculation chain, no fast1 / rep1.  Called behind first_degrees with a
+  // non-empty start list.  GO 1 STEPS reports a deferred compile error at its only step, so here
+  // it comes before any hop.
+  int32_t run_upto() {
+    if (deferred != NBG_OK) throw Error(deferred, deferred_msg);
+    return s.distinct ? upto_distinct() : upto_rows();
+  }
+  // the query's end behind the final step(s): ev[1] ends the device time (read when asked for)
+  int32_t upto_hand_out() {
+    if (tot_ev) hipEventRecord(c.ev[1], c.stream);
+    c.total_pending = tot_ev;
+    return hand_out(pack_strings());
+  }
+
+  // DISTINCT: the result depends only on the set of vertices that are in some step's frontier,
+  // U = starts + everything reached within N - 1 hops (with out-edges), so a visited-pruned BFS
+  // builds U expanding each vertex once (levels B_k) and ONE final step runs over U.
+  int32_t upto_distinct() {
+    if (!es.odeg.p) throw Error(NBG_E_STATE, "GO UPTO: the snapshot has no out-degree array");
+    const size_t bm = size_t(map_bytes(c) / 8 + 64);
+    c.ws_vis.ensure(2 * bm);
+    auto* vis = c.ws_vis.as<unsigned long long>();
+    auto* uni = reinterpret_cast<unsigned long long*>(c.ws_vis.as<uint8_t>() + bm);
+    // B_1: the frontier bitmap resolve_starts left (the distinct starts with out-edges; a start
+    // without them yields nothing at any step, and reaching it again is harmless)
+    const size_t wb = size_t((n_own + 63) / 64) * 8;
+    NBG_HIP(hipMemcpyAsync(vis, bitsA, wb, hipMemcpyDeviceToDevice, c.stream));
+    NBG_HIP(hipMemcpyAsync(uni, bitsA, wb, hipMemcpyDeviceToDevice, c.stream));
+    const uint32_t* odeg = es.odeg.as<uint32_t>();
+    unsigned long long* const S = K.d + kCntUpto;
+    // one lane a row, at most upto_grid blocks adding their sums into ks shards (RMAT-26, UPTO 3
+    // query: 1024 blocks 0.985 ms, 2048 / 4096 / 8192 0.799, 16384 0.925; 4096 unsharded 0.842)
+    const int grid = grid_cap((n_own + 63) / 64 * 64, 256, int(std::max<int64_t>(1, c.opt("upto_grid", 4096))));
+    // a level's successor is certainly expanded top-down: the claim writes it as a list too
+    const bool td_certain = !bu_ok || bu_force < 0;
+    const int64_t n_scan = std::min<int64_t>(n_own, es.bu_in_tiles * 128);  // rows with an in-edge lie below
+    int64_t bn = nF;                     // |B_k| on this rank
+    int64_t un = nF, ue = E, ueg = Eg;   // |U|, outdeg(U) on this rank, outdeg(U) over ranks
+    for (int32_t step = 1; step < s.steps && Eg > 0; step++) {
+      c.timing.steps_run++;
+      c.timing.edges_scanned += uint64_t(E);
+      c.timing.expand_launches++;
+      const bool bu = want_bu(Eg);  // (global: every rank takes the same branch)
+      if (!bu) ensure_off();  // (may count the list at kCntList: ahead of the hop's zeroing)
+      NBG_HIP(hipMemsetAsync(K.d, 0, kShardStride * size_t(ks) * 8, c.stream));  // the hop's sums and kCntList
+      if (ks > 1) shards_dirty = true;
+      int32_t* nl = nullptr;
+      if (bu) {
+        const uint32_t* fb = global_bits(c, bitsA);
+        const size_t ia = timing_event(c);
+        k_upto_bu<<<grid, 256, 0, c.stream>>>(es.tr.row_ptr.as<int64_t>(), es.tr.col.as<int32_t>(),
+                                              std::min<int64_t>(n_own, es.tr.n_rows), n_scan, fb, c.n_global, odeg, vis,
+                                              uni, reinterpret_cast<unsigned long long*>(bitsB), S, ks);
+        NBG_HIP(hipGetLastError());
+        c.tpend.push_back(Ctx::PendingTime{ia, timing_event(c), c.timing.n_hops, 0});
+        c.timing.bu_steps++;
+      } else {
+        frontier_args();
+        if (E > 0) {
+          launch_expand<EXP_MARK>(c, a, PK_NONE, no_fp, nullptr, env, E);
+          c.timing.expand_bytes += expand_bytes(nF, E, 0, EXP_MARK);
+        }
+        exchange_marks(c, map);  // several ranks: every owner receives the marks of its vertices
+        if (td_certain) nl = c.ws_front[cur ^ 1].as<int32_t>();
+        const size_t ia = timing_event(c);
+        k_upto_claim<<<grid, 256, 0, c.stream>>>(map + lo, n_own, map_bound, odeg, vis, uni,
+                                                 reinterpret_cast<unsigned long long*>(bitsB), nl, K.d + kCntList, S, ks);
+        NBG_HIP(hipGetLastError());
+        c.tpend.push_back(Ctx::PendingTime{ia, timing_event(c), c.timing.n_hops, 0});
+      }
+      if (multi) dev_allsum(c, K.d, {kCntUpto, kCntUpto + 1}, K.d + kCntGlobal);
+      fetch_counters(c, K.d, kCntUpto + 4, K.h, nullptr, ks);
+      const unsigned long long* h = K.h + kCntUpto;
+      const int64_t read = bu ? int64_t(h[3]) : E;
+      // bottom-up: 4 B per entry read, a row_ptr pair per open row (not counted: unknown), vis,
+      // frontier and next words; claim: the mark bytes read, vis / uni / next words
+      c.timing.expand_bytes += bu ? uint64_t(h[3]) * 4 + 3 * uint64_t(n_scan / 8) : uint64_t(map_bound) + 2 * uint64_t(n_own / 8);
+      const unsigned long long hs[8] = {h[0], h[1], (unsigned long long)bn, (unsigned long long)read, 0, 0, 0, 0};
+      c.timing.hop(bu ? 1 : 0, false, 0.0, hs);
+      c.timing.name_last_hop(bu ? "nbg::k_upto_bu" : "nbg::k_upto_claim", bu ? "" : "nbg::k_expand");
+      // the next level: the bitmap the kernel wrote (and the claim's list)
+      std::swap(bitsA, bitsB);
+      bn = int64_t(h[2]);
+      E = E_known = int64_t(h[1]);
+      Eg = multi ? int64_t(K.h[kCntGlobal + 1]) : E;
+      off_ready = false;
+      if (nl) {
+        cur ^= 1;
+        F = nl;
+        nF = int64_t(K.h[kCntList]);
+        have_list = true;
+        list_n = -1;
+      } else {
+        have_list = false;
+        list_n = bn;
+      }
+      un += bn, ue += E, ueg += Eg;
+      if ((multi ? K.h[kCntGlobal] : h[0]) == 0) break;  // nothing new anywhere: U is complete
+    }
+    // ---- the final step over U.  U holds the starts, which need no in-edge: no consumer may
+    // assume a hop's output here (launch_bu_lean's hop_front, map_bound on the frontier) ----
+    c.timing.steps_run++;
+    clean_shards();  // dense counters from here on
+    bitsA = reinterpret_cast<uint32_t*>(uni);
+    have_list = false;
+    list_n = un;
+    off_ready = false;
+    E = E_known = ue;
+    Eg = ueg;
+    begin_final();
+    if (lone_dst) final_distinct_dst();
+    else final_rows();
+    return upto_hand_out();
+  }
+
+  // Without DISTINCT multiplicity matters: the frontiers are the unpruned F_k of the existing
+  // hops.  Each step's frontier first yields its rows (final_rows), then advances (one expansion
+  // each; no step is re-run from the starts); the steps' columns stay on the device and are
+  // concatenated at the end.  The general path: existing kernels, not a tuned one.
+  int32_t upto_rows() {
+    struct StepRows {
+      std::vector<DevBuf> cols, slen;
+      int64_t n = 0;
+    };
+    std::vector<StepRows> parts;
+    for (int32_t step = 1; step <= s.steps && Eg > 0; step++) {
+      c.timing.steps_run++;
+      // step 1 rescans duplicate starts exactly as GO 1 STEPS does (k_list_starts); the advance
+      // below uses the de-duplicated frontier
+      const bool dup = step == 1 && hop1_scanned >= 0 && hop1_scanned != E;
+      int32_t* const keepF = F;
+      const int64_t keepN = nF, keepE = E;
+      DevBuf dl;
+      if (dup) {
+        dl.alloc(size_t(ns + 64) * 4);
+        NBG_HIP(hipMemsetAsync(K.d + kCntList, 0, 8, c.stream));
+        k_list_starts<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, row_ptr, row_ok, dl.as<int32_t>(),
+                                                         K.d + kCntList);
+        NBG_HIP(hipGetLastError());
+        fetch_counters(c, K.d, kCntList + 1, K.h);
+        F = dl.as<int32_t>();
+        nF = int64_t(K.h[kCntList]);
+        E = E_known = hop1_scanned;  // the list's out-degree sum (k_starts_degree)
+        off_ready = false;
+      }
+      begin_final();  // (counts the step's E entries as scanned)
+      final_rows();
+      StepRows sr;
+      sr.cols = std::move(rows->dev);
+      sr.slen = std::move(slen);
+      sr.n = nrows;
+      parts.push_back(std::move(sr));
+      if (dup) {
+        F = keepF, nF = keepN, E = E_known = keepE;
+        off_ready = false;
+      }
+      if (step == s.steps) break;
+      if (want_bu(Eg)) hop_bottom_up(step);
+      else hop_top_down(step);
+      if (nset_global == 0) break;  // the frontier died: the rows of the steps so far
+    }
+    if (parts.empty()) return finish_empty();  // no start has out-edges
+    int64_t total = 0;
+    for (auto& p : parts) total += p.n;
+    rows = std::make_unique<HostRows>();
+    slen.clear();
+    slen.resize(yields.size());
+    for (size_t k = 0; k < yields.size(); k++) {
+      const int32_t t = yields[k].result_type;
+      const size_t w = t == VT_BOOL ? 1 : 8;
+      DevBuf b;
+      b.alloc(size_t(total + 1) * w);
+      if (t == VT_STR) slen[k].alloc(size_t(total + 1) * 8);
+      int64_t at = 0;
+      for (auto& p : parts) {
+        if (p.n) {
+          NBG_HIP(hipMemcpyAsync(b.as<uint8_t>() + size_t(at) * w, p.cols[k].p, size_t(p.n) * w, hipMemcpyDeviceToDevice,
+                                 c.stream));
+          if (t == VT_STR)
+            NBG_HIP(hipMemcpyAsync(slen[k].as<int64_t>() + at, p.slen[k].p, size_t(p.n) * 8, hipMemcpyDeviceToDevice,
+                                   c.stream));
+        }
+        at += p.n;
+      }
+      rows->types.push_back(result_type(t));
+      rows->dev.push_back(std::move(b));
+    }
+    nrows = total;
+    return upto_hand_out();
+  }
 };
 
 }  // namespace
@@ -4233,6 +4560,7 @@ int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
   PoolScope pool_scope(query_pool(c));
   if (!c.finalized) throw Error(NBG_E_STATE, "snapshot not finalized");
   if (s.steps < 1) throw Error(NBG_E_INVALID_ARG, "steps must be >= 1");
+  if (s.upto != 0 && s.upto != 1) throw Error(NBG_E_INVALID_ARG, "upto must be 0 or 1");
   if (s.edge_type <= 0) throw Error(NBG_E_INVALID_ARG, "GO ... REVERSELY is not supported (GoExecutor.cpp:203-205)");
   auto it = c.edges.find(s.edge_type);
   if (it == c.edges.end()) throw Error(NBG_E_INVALID_ARG, "edge type not in snapshot");
@@ -4251,6 +4579,7 @@ int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
   if (q.nset_global == 0) return q.finish_empty();
   q.bind_inputs();
   q.first_degrees();
+  if (q.upto) return q.run_upto();
   for (int32_t step = 1; step < s.steps; step++) {
     c.timing.steps_run++;
     q.clean_shards();  // (the speculated hops' sums were fetched: dense counters from here on)

@@ -372,9 +372,10 @@ class GraphSpace:
         return names, types, cols, offs, keep
 
     def go(self, starts, steps: int, edge_type: int, where=None, yields: Iterable = (), distinct: bool = False,
-           keep_on_device: bool = False, inputs=None) -> RowSet:
+           keep_on_device: bool = False, inputs=None, upto: bool = False) -> RowSet:
         """GO ... FROM starts. `inputs`: the piped / variable rows ($-.prop / $var.prop), one per start,
-        as [(name, NBG_T_*, values)] (GoExecutor::getPropFromInterim)."""
+        as [(name, NBG_T_*, values)] (GoExecutor::getPropFromInterim).  `upto`: GO UPTO `steps` STEPS,
+        the rows of GO 1 .. `steps` STEPS together (include/nebula_amd.h)."""
         starts = np.ascontiguousarray(starts, dtype=np.int64)
         w = X.encode(where)
         ys = tuple(X.encode(y) for y in yields)
@@ -382,7 +383,7 @@ class GraphSpace:
         # flags) re-uses its prepared spec: building it cost ~15 us of Python per call (numpy's
         # ctypes pointer views), time the device sat idle between two queries.  The spec points at
         # the array's data, so values changed in place are read as they are at the call.
-        ckey = (id(starts), len(starts), w, ys, steps, edge_type, bool(distinct), bool(keep_on_device))
+        ckey = (id(starts), len(starts), w, ys, steps, edge_type, bool(distinct), bool(keep_on_device), bool(upto))
         if not inputs and self._last_spec is not None and self._last_spec[0] == ckey:
             spec = self._last_spec[1]
             rows = _lib.Rows()
@@ -404,6 +405,7 @@ class GraphSpace:
         wb, _, yp, yl = views
         spec = _lib.GoSpec(edge_type, steps, _p(starts), len(starts), _p(wb), len(w), yp, yl, len(ys),
                            int(distinct), int(keep_on_device))
+        spec.upto = int(bool(upto))
         if inputs:
             names, types, cols, offs, _keep = self._input_table(inputs, len(starts))
             spec.n_inputs = len(inputs)
@@ -682,16 +684,17 @@ class AddVerticesProcessor(_WriteProcessor):
 
 
 class GoExecutor:
-    """GO [N STEPS] FROM starts OVER edge [WHERE f] [YIELD [DISTINCT] cols]."""
+    """GO [[UPTO] N STEPS] FROM starts OVER edge [WHERE f] [YIELD [DISTINCT] cols]."""
 
     def __init__(self, space: GraphSpace, starts, edge_type: int, steps: int = 1, where=None, yields=(),
-                 distinct: bool = False):
+                 distinct: bool = False, upto: bool = False):
         self.space, self.starts, self.edge_type = space, starts, edge_type
         self.steps, self.where, self.yields, self.distinct = steps, where, list(yields), distinct
+        self.upto = upto
 
     def execute(self, keep_on_device: bool = False) -> RowSet:
         return self.space.go(self.starts, self.steps, self.edge_type, self.where, self.yields, self.distinct,
-                             keep_on_device)
+                             keep_on_device, upto=self.upto)
 
 
 class FindPathExecutor:

@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--hops", type=int, default=3)
     ap.add_argument("--where", type=int, default=499)
     ap.add_argument("--plain", action="store_true")
+    ap.add_argument("--upto", action="store_true", help="GO UPTO --hops STEPS")
     ap.add_argument("--option", action="append", default=[])
     args = ap.parse_args()
     from nebula_amd import GraphSpace, synth
@@ -39,7 +40,7 @@ def main():
     for _ in range(args.reps):
         t = time.perf_counter()
         r = sp.go(starts, args.hops, 1, where=where, yields=[X.EdgeDst("follow")], distinct=not args.plain,
-                  keep_on_device=True)
+                  keep_on_device=True, upto=args.upto)
         ms.append((time.perf_counter() - t) * 1e3)
     tm = sp.last_timing()
     print(json.dumps({"options": args.option, "ms": ms, "rows": r.n_rows,
