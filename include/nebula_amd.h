@@ -289,6 +289,35 @@ int32_t nbg_go(nbg_ctx* ctx, const nbg_go_spec* spec, nbg_rows* out);
 int32_t nbg_shortest_path(nbg_ctx* ctx, int32_t edge_type, const int64_t* src,
                           const int64_t* dst, size_t npairs, int32_t max_steps, nbg_rows* out);
 
+/* ---- ORDER BY -----------------------------------------------------------------------------
+ * Replaces OrderByExecutor::execute (src/graph/OrderByExecutor.cpp:104-136: std::sort of the
+ * piped rows under the factor comparator) on a result table: `GO ... | ORDER BY $-.col [ASC|DESC],
+ * ...`.  in: a plain row table as nbg_go hands it out, host-resident (its columns are uploaded)
+ * or device-resident (on_device = 1, produced on this context); it is neither consumed nor
+ * modified, and the caller frees both in and out.  A table carrying row_vertex, vertices, failed
+ * parts or paths is NBG_E_INVALID_ARG.  Factor f orders by column cols[f], descending when
+ * desc[f] = 1; factor 0 is the most significant.  Resolving `$-.name` to an index, and dropping
+ * names the input does not have (OrderByExecutor.cpp:91-101), is the caller's job.  n_factors = 0
+ * returns the rows in input order (OrderByTest.WrongFactor); a column's later repeats decide
+ * nothing.  A column index out of range or desc outside {0, 1} is NBG_E_INVALID_ARG.
+ * Order (ColumnValue::operator<, OrderByExecutor.cpp:14-68): VID / INT / TIMESTAMP as signed
+ * int64, BOOL false < true, DOUBLE numeric, STRING as std::string (unsigned bytes, a proper prefix
+ * first, embedded NUL bytes legal).  DESC is the exact reverse.  Owned by this build (DESIGN.md
+ * divergence 8): the sort is stable (rows equal under every factor keep their input order; the
+ * reference's std::sort leaves it open), -0.0 ties with +0.0, every NaN ties with every NaN and
+ * sorts after +inf under ASC.
+ * out: the same column types, in HBM when keep_on_device = 1, else on the host (STRING columns as
+ * packed bytes + n_rows+1 offsets); zero input rows give zero rows.  edges_scanned is copied.
+ * NBG_E_UNSUPPORTED: a STRING factor with a value longer than 256 bytes; 2^32 rows or more.
+ * NBG_E_NOMEM: the workspace (24 B per row + the output) did not fit; the input is untouched.
+ * Works on any context (no snapshot needed).  Rank-local: with world_size > 1 each rank orders
+ * the rows it holds and no collective is issued; merging the ranks' runs stays with the caller.
+ * nbg_last_timing then reports total_ms (a host table's upload, the sort and the output
+ * permutation; the copies to the host behind them are not in it), launches (kernels; a scan counts as one), steps_run (radix
+ * passes that ran), host_waits (one per 64-bit key sorted, plus the hand-out) and n_hops = 0.   */
+int32_t nbg_order_by(nbg_ctx* ctx, const nbg_rows* in, const int32_t* cols, const int32_t* desc,
+                     size_t n_factors, int32_t keep_on_device, nbg_rows* out);
+
 /* ---- timing of the last call (HIP events on the engine stream) --------------------------- */
 /* one hop of the last nbg_go: mode 0 = top-down expansion of a frontier list, 1 = bottom-up
  * over the transposed CSR.  c[]: top-down {frontier, entries, next frontier, 0, 0, 0};
@@ -335,7 +364,7 @@ typedef struct {
                              nbg_shortest_path: batches that ran device-driven (the others ran
                              host-driven: option sp_dev = 0, or a list overflow re-ran them)   */
   int32_t launches;       /* nbg_shortest_path: kernel launches of its device-driven batches
-                             (ABI 5; 0 for other calls)                                         */
+                             (ABI 5); nbg_order_by: its kernel launches; 0 for other calls      */
   int32_t comm_calls;     /* collectives this rank issued through its communicator in the last
                              call (ABI 6; comm_ms / comm_calls = the mean time of one on the
                              engine stream, enqueue to completion)                              */

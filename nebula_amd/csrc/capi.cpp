@@ -357,6 +357,17 @@ int32_t nbg_shortest_path(nbg_ctx* ctx, int32_t edge_type, const int64_t* src, c
   });
 }
 
+int32_t nbg_order_by(nbg_ctx* ctx, const nbg_rows* in, const int32_t* cols, const int32_t* desc, size_t n_factors,
+                     int32_t keep_on_device, nbg_rows* out) {
+  return guarded(ctx, [&](Ctx& c) {
+    if (!in || !out || in == out || (n_factors && (!cols || !desc))) throw Error(NBG_E_INVALID_ARG, "bad arguments");
+    memset(out, 0, sizeof(*out));
+    const int32_t rc = nbg::order_by_run(c, *in, cols, desc, n_factors, keep_on_device, out);
+    nbg::timing_resolve(c);
+    return rc;
+  });
+}
+
 int32_t nbg_last_timing(nbg_ctx* ctx, nbg_timing* out) {
   return guarded(ctx, [&](Ctx& c) {
     if (!out) throw Error(NBG_E_INVALID_ARG, "null out");

@@ -7,6 +7,8 @@
                            src/storage/QueryBoundProcessor.h:23-28 / QueryBaseProcessor.h:47.
 * ``GoExecutor``        -- GO N STEPS FROM ... OVER ... [WHERE] [YIELD [DISTINCT]], the
                            device-resident replacement of src/graph/GoExecutor.cpp:80-782.
+* ``OrderByExecutor``   -- ``... | ORDER BY $-.col [ASC|DESC], ...`` on a result table, the device
+                           replacement of src/graph/OrderByExecutor.cpp:70-136.
 * ``FindPathExecutor``  -- FIND SHORTEST PATH FROM ... TO ... OVER ... UPTO N STEPS (the
                            reference's FindExecutor is a stub, src/graph/FindExecutor.cpp:20-22;
                            semantics in include/nebula_amd.h), batched bidirectional BFS.
@@ -79,7 +81,10 @@ class RowSet:
     INT / VID / DOUBLE columns are views of the engine's pinned result blocks, not copies; the
     rows are freed when the RowSet and every such column are gone."""
 
-    def __init__(self, rows: _lib.Rows, keep_device: bool = False, holder: _RowsHandle | None = None):
+    def __init__(self, rows: _lib.Rows, keep_device: bool = False, holder: _RowsHandle | None = None,
+                 raw_strings: bool = False):
+        # raw_strings: STRING values as bytes (order_by on tables whose strings are not UTF-8 text)
+        self._holder = holder  # a device table handed on to order_by stays alive with the RowSet
         self.n_rows = int(rows.n_rows)
         self.types = [rows.col_types[i] for i in range(rows.n_cols)]
         self.edges_scanned = int(rows.edges_scanned)
@@ -108,7 +113,8 @@ class RowSet:
             elif t == _lib.T_STRING:
                 offs = np.ctypeslib.as_array(rows.str_offsets[c], shape=(self.n_rows + 1,)).copy()
                 raw = C.string_at(ptr, int(offs[-1])) if self.n_rows else b""
-                self.columns.append([raw[offs[i]:offs[i + 1]].decode() for i in range(self.n_rows)])
+                vals = [raw[offs[i]:offs[i + 1]] for i in range(self.n_rows)]
+                self.columns.append(vals if raw_strings else [v.decode() for v in vals])
             elif self.n_rows == 0:
                 self.columns.append(np.zeros(0, dtype=np.uint8 if t == _lib.T_BOOL else
                                              (np.float64 if t == _lib.T_DOUBLE else np.int64)))
@@ -372,11 +378,17 @@ class GraphSpace:
         return names, types, cols, offs, keep
 
     def go(self, starts, steps: int, edge_type: int, where=None, yields: Iterable = (), distinct: bool = False,
-           keep_on_device: bool = False, inputs=None, upto: bool = False) -> RowSet:
+           keep_on_device: bool = False, inputs=None, upto: bool = False, order_by=None) -> RowSet:
         """GO ... FROM starts. `inputs`: the piped / variable rows ($-.prop / $var.prop), one per start,
         as [(name, NBG_T_*, values)] (GoExecutor::getPropFromInterim).  `upto`: GO UPTO `steps` STEPS,
-        the rows of GO 1 .. `steps` STEPS together (include/nebula_amd.h)."""
+        the rows of GO 1 .. `steps` STEPS together (include/nebula_amd.h).  `order_by`:
+        [(column index, desc)] -- GO ... | ORDER BY: the result stays in HBM, nbg_order_by orders it
+        there, and `keep_on_device` applies to the ordered table."""
         starts = np.ascontiguousarray(starts, dtype=np.int64)
+        want_device = keep_on_device
+        if order_by is not None:
+            order_by = [(int(c), int(d)) for c, d in order_by]
+            keep_on_device = True  # the GO itself; the repeated-call key below sees this flag
         w = X.encode(where)
         ys = tuple(X.encode(y) for y in yields)
         # a call repeating the previous one's arguments (the same start array object, plan and
@@ -388,7 +400,7 @@ class GraphSpace:
             spec = self._last_spec[1]
             rows = _lib.Rows()
             self._check(self.L.nbg_go(self.h, C.byref(spec), C.byref(rows)))
-            return self._go_rows(rows, keep_on_device)
+            return self._go_rows(rows, want_device, order_by)
         # the C views of the encoded WHERE / YIELD bytes, built once per distinct plan (a GO
         # repeated with the same plan re-uses them; they live as long as the space)
         key = (w, ys)
@@ -415,9 +427,14 @@ class GraphSpace:
             self._last_spec = (ckey, spec, starts)  # (the array is held while the spec points at it)
         rows = _lib.Rows()
         self._check(self.L.nbg_go(self.h, C.byref(spec), C.byref(rows)))
-        return self._go_rows(rows, keep_on_device)
+        return self._go_rows(rows, want_device, order_by)
 
-    def _go_rows(self, rows, keep_on_device: bool) -> RowSet:
+    def _go_rows(self, rows, keep_on_device: bool, order_by=None) -> RowSet:
+        if order_by is not None:
+            try:
+                return self._order_rows(rows, order_by, keep_on_device)
+            finally:
+                self.L.nbg_rows_free(C.byref(rows))  # the unordered intermediate
         if keep_on_device:
             try:
                 return RowSet(rows)
@@ -426,6 +443,74 @@ class GraphSpace:
         # host result: zero-copy views of the pinned blocks, held until the columns are dropped
         return RowSet(rows, holder=_RowsHandle(self.L, rows))
 
+    def _order_rows(self, rows: _lib.Rows, factors, keep_on_device: bool, raw_strings: bool = False) -> RowSet:
+        """nbg_order_by on an nbg_rows (host or device); the input stays the caller's."""
+        nf = len(factors)
+        cols = (C.c_int32 * max(nf, 1))(*[int(c) for c, _ in factors])
+        desc = (C.c_int32 * max(nf, 1))(*[int(d) for _, d in factors])
+        out = _lib.Rows()
+        self._check(self.L.nbg_order_by(self.h, C.byref(rows), C.cast(cols, C.c_void_p), C.cast(desc, C.c_void_p), nf,
+                                        int(bool(keep_on_device)), C.byref(out)))
+        # held until the RowSet (and every column viewing a pinned block) is gone; a device table
+        # stays usable as the input of a further order_by
+        return RowSet(out, holder=_RowsHandle(self.L, out), raw_strings=raw_strings)
+
+    def order_by(self, table, factors, keep_on_device: bool = False) -> RowSet:
+        """ORDER BY on a result table (nbg_order_by): stable, factor 0 the most significant.
+        `table`: a RowSet (on the host, or an ordered one kept in HBM), or [(NBG_T_*, values)] columns
+        for a synthetic table (STRING values as str or bytes; bytes in give bytes out).
+        `factors`: [(column index, desc)]."""
+        factors = [(int(c), int(d)) for c, d in factors]
+        if isinstance(table, RowSet):
+            if table.on_device:
+                if table._holder is None or table._holder.rows is None:
+                    raise ValueError("order_by: this device RowSet no longer owns its columns")
+                return self._order_rows(table._holder.rows, factors, keep_on_device)
+            columns = list(zip(table.types, table.columns))
+            n = table.n_rows
+        else:
+            columns = [(int(t), v) for t, v in table]
+            n = len(columns[0][1]) if columns else 0
+        raw = False
+        rows = _lib.Rows()
+        nc = len(columns)
+        types = (C.c_int32 * max(nc, 1))(*[t for t, _ in columns])
+        cols = (C.c_void_p * max(nc, 1))()
+        offs = (C.POINTER(C.c_int64) * max(nc, 1))()
+        keep = []
+        for i, (t, vals) in enumerate(columns):
+            if len(vals) != n:
+                raise ValueError(f"order_by: column {i} has {len(vals)} rows, column 0 has {n}")
+            if t == _lib.T_STRING:
+                raw |= any(isinstance(v, (bytes, bytearray)) for v in vals)
+                bs = [v.encode() if isinstance(v, str) else bytes(v) for v in vals]
+                o = np.zeros(n + 1, dtype=np.int64)
+                if bs:
+                    o[1:] = np.cumsum([len(b) for b in bs])
+                blob = np.frombuffer(b"".join(bs) + b"\0" * 8, dtype=np.uint8)
+                cols[i] = blob.ctypes.data
+                offs[i] = o.ctypes.data_as(C.POINTER(C.c_int64))
+                keep += [blob, o]
+            else:
+                dt = np.float64 if t == _lib.T_DOUBLE else np.uint8 if t == _lib.T_BOOL else np.int64
+                a = np.ascontiguousarray(vals, dtype=dt)
+                if a.size == 0:
+                    a = np.zeros(1, dtype=dt)
+                cols[i] = a.ctypes.data
+                keep.append(a)
+        rows.n_rows, rows.n_cols, rows.on_device = n, nc, 0
+        rows.col_types, rows.cols, rows.str_offsets = types, cols, offs
+        if isinstance(table, RowSet):
+            # a get_bound response is not a plain row table: its parts travel along, and the call
+            # refuses them (NBG_E_INVALID_ARG)
+            if len(table.row_vertex):
+                rv = np.ascontiguousarray(table.row_vertex, dtype=np.int64)
+                rows.row_vertex = rv.ctypes.data_as(C.POINTER(C.c_int64))
+                keep.append(rv)
+            rows.n_vertices = len(table.vertex_ids)
+            rows.n_failed = len(table.failed)
+            rows.n_vertex_cols = len(table.vertex_columns)
+        return self._order_rows(rows, factors, keep_on_device, raw_strings=raw)
 
     def shortest_path(self, src, dst, edge_type: int, max_steps: int = 5) -> "PathResult":
         """Pairwise shortest paths (src[i] -> dst[i]) over edge_type out-edges."""
@@ -687,14 +772,43 @@ class GoExecutor:
     """GO [[UPTO] N STEPS] FROM starts OVER edge [WHERE f] [YIELD [DISTINCT] cols]."""
 
     def __init__(self, space: GraphSpace, starts, edge_type: int, steps: int = 1, where=None, yields=(),
-                 distinct: bool = False, upto: bool = False):
+                 distinct: bool = False, upto: bool = False, order_by=None):
         self.space, self.starts, self.edge_type = space, starts, edge_type
         self.steps, self.where, self.yields, self.distinct = steps, where, list(yields), distinct
         self.upto = upto
+        self.order_by = order_by  # [(column index, desc)]: ... | ORDER BY, ordered on the device
 
     def execute(self, keep_on_device: bool = False) -> RowSet:
         return self.space.go(self.starts, self.steps, self.edge_type, self.where, self.yields, self.distinct,
-                             keep_on_device, upto=self.upto)
+                             keep_on_device, upto=self.upto, order_by=self.order_by)
+
+
+ASC, DESC = 0, 1  # OrderFactor::OrderType (src/parser/TraverseSentences.h)
+
+
+class OrderByExecutor:
+    """... | ORDER BY $-.name [ASC|DESC], ...  (OrderByExecutor, src/graph/OrderByExecutor.cpp).
+    `factors`: [(name, desc)] with names written `$-.name` or `name`, desc as 0 / 1, bool or
+    "ASC" / "DESC"; `columns`: the input's column names (the YIELD aliases).  feedResult's name
+    resolution (OrderByExecutor.cpp:88-101) runs here on the host: a name the input does not have
+    is dropped, so a sentence whose names are all unknown leaves the rows in input order.
+    `space` may be None for resolution alone."""
+
+    def __init__(self, space, factors, columns):
+        self.space, self.columns = space, list(columns)
+        self.sort_factors = []  # [(column index, desc)], as nbg_order_by takes them
+        for name, desc in factors:
+            field = name[3:] if name.startswith("$-.") else name
+            if field not in self.columns:
+                continue
+            if isinstance(desc, str):
+                if desc.upper() not in ("ASC", "DESC"):
+                    raise ValueError(f"order type {desc!r}")
+                desc = desc.upper() == "DESC"
+            self.sort_factors.append((self.columns.index(field), int(bool(desc))))
+
+    def execute(self, rowset, keep_on_device: bool = False) -> RowSet:
+        return self.space.order_by(rowset, self.sort_factors, keep_on_device)
 
 
 class FindPathExecutor:
