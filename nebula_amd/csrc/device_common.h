@@ -89,6 +89,12 @@ __device__ inline void hub_fill(uint32_t* s_fb, const uint32_t* __restrict__ fbi
   __syncthreads();
 }
 
+__device__ inline unsigned long long wave_sum_u64(unsigned long long x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+  return x;
+}
+
 // wave-aggregated append: returns this lane's slot in `*counter` space (lanes with !pred get -1)
 __device__ inline int64_t wave_append(unsigned long long* counter, bool pred) {
   uint64_t mask = __ballot(pred);

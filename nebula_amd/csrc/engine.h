@@ -12,10 +12,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <chrono>
-#include <cstdint>
 #include <atomic>
 #include <chrono>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -41,25 +40,17 @@ struct Error : std::runtime_error {
       throw ::nbg::Error(NBG_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_));   \
   } while (0)
 
-// Device buffer (RAII).  Never resized inside a launch sequence that a caller may capture.
-// Per-context cache of device blocks used while a query runs: queries allocate and drop many
-// temporaries, and hipFree synchronises the whole device, so blocks freed during a query go
-// back to the context's pool and are reused by later queries on the same stream (stream order
-// makes the reuse safe).  Blocks allocated outside a query scope (the snapshot) use
-// hipMalloc/hipFree directly.
-struct BufPool;
-void pool_register(BufPool* p, bool add);
-size_t pool_trim_all();  // every live pool's cache back to the driver (an out-of-memory retry)
-struct BufPool {
+// Size-keyed cache of freed blocks behind BufPool (device, hipFree) and HostPool (pinned host,
+// hipHostFree): get() hands out a block of at least `want` bytes that is not wastefully larger,
+// put() keeps a block while the cache stays under `limit`
+template <hipError_t (*FREE)(void*)>
+struct BlockCache {
   std::mutex mu;
   std::multimap<size_t, void*> blocks;
   size_t cached = 0;
-  size_t limit = size_t(16) << 30;
-  BufPool() { pool_register(this, true); }
-  ~BufPool() {
-    pool_register(this, false);
-    for (auto& b : blocks) (void)hipFree(b.second);
-  }
+  size_t limit;
+  explicit BlockCache(size_t lim) : limit(lim) {}
+  ~BlockCache() { trim(); }
   void* get(size_t want, size_t& got) {
     std::lock_guard<std::mutex> lk(mu);
     auto it = blocks.lower_bound(want);
@@ -79,17 +70,30 @@ struct BufPool {
         return;
       }
     }
-    (void)hipFree(p);
+    (void)FREE(p);
   }
   // hand every cached block back to the driver (a failed hipMalloc retries after this)
   size_t trim() {
     std::lock_guard<std::mutex> lk(mu);
     const size_t freed = cached;
-    for (auto& b : blocks) (void)hipFree(b.second);
+    for (auto& b : blocks) (void)FREE(b.second);
     blocks.clear();
     cached = 0;
     return freed;
   }
+};
+// Device buffer (RAII).  Never resized inside a launch sequence that a caller may capture.
+// Per-context cache of device blocks used while a query runs: queries allocate and drop many
+// temporaries, and hipFree synchronises the whole device, so blocks freed during a query go
+// back to the context's pool and are reused by later queries on the same stream (stream order
+// makes the reuse safe).  Blocks allocated outside a query scope (the snapshot) use
+// hipMalloc/hipFree directly.
+struct BufPool;
+void pool_register(BufPool* p, bool add);
+size_t pool_trim_all();  // every live pool's cache back to the driver (an out-of-memory retry)
+struct BufPool : BlockCache<hipFree> {
+  BufPool() : BlockCache(size_t(16) << 30) { pool_register(this, true); }
+  ~BufPool() { pool_register(this, false); }
 };
 extern thread_local std::shared_ptr<BufPool> tl_pool;  // set for the duration of a query
 
@@ -100,39 +104,8 @@ extern thread_local std::shared_ptr<BufPool> tl_pool;  // set for the duration o
 // Cap (set per query, host_pool_cap): option host_pool_gb, else 1/16 of the host's RAM shared
 // among the contexts on the device, at most 8 GiB (eight in-process LocalComm ranks on a 1.5 TB
 // host: 8 GiB each; on a 64 GiB host: 512 MiB each).  Trimmed when the context is destroyed.
-struct HostPool {
-  std::mutex mu;
-  std::multimap<size_t, void*> blocks;
-  size_t cached = 0;
-  size_t limit = size_t(8) << 30;
-  ~HostPool() { trim(); }
-  void trim() {
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& b : blocks) (void)hipHostFree(b.second);
-    blocks.clear();
-    cached = 0;
-  }
-  void* get(size_t want, size_t& got) {
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = blocks.lower_bound(want);
-    if (it == blocks.end() || it->first > 2 * want + (size_t(1) << 20)) return nullptr;
-    got = it->first;
-    void* p = it->second;
-    blocks.erase(it);
-    cached -= got;
-    return p;
-  }
-  void put(void* p, size_t cap) {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      if (cached + cap <= limit) {
-        blocks.emplace(cap, p);
-        cached += cap;
-        return;
-      }
-    }
-    (void)hipHostFree(p);
-  }
+struct HostPool : BlockCache<hipHostFree> {
+  HostPool() : BlockCache(size_t(8) << 30) {}
 };
 struct HostBuf {
   void* p = nullptr;
@@ -690,13 +663,15 @@ void resolve_total(Ctx& c);
 int32_t go_run(Ctx& c, const nbg_go_spec& spec, nbg_rows* out);
 // the out CSR replica and its out-degrees (collective: every rank calls it at the same point)
 void ensure_rep_out(Ctx& c, EdgeSpace& es);
+void timing_reset(Ctx& c);
+void timing_resolve(Ctx& c);
+// bound.hip
 int32_t get_bound_run(Ctx& c, int32_t et, const int32_t* parts, const int64_t* vids, size_t n,
                       const uint8_t* filter, size_t flen, const nbg_prop_def* cols, size_t ncols,
                       nbg_rows* out, const int32_t* stats = nullptr);
+// paths.hip
 int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src, const int64_t* dst, size_t n,
                           int32_t max_steps, nbg_rows* out);
-void timing_reset(Ctx& c);
-void timing_resolve(Ctx& c);
 // order.hip
 int32_t order_by_run(Ctx& c, const nbg_rows& in, const int32_t* cols, const int32_t* desc, size_t n_factors,
                      int32_t keep_on_device, nbg_rows* out);

@@ -21,6 +21,7 @@
 
 #include "engine.h"
 #include "order_keys.h"
+#include "query_common.h"
 #include "rows.h"
 
 namespace nbg {
@@ -405,10 +406,7 @@ struct OrderSort {
     if (items == 4) k_ord_count<4><<<ntiles, kOrdThreads, 0, c.stream>>>(s, n, shift, cnt, ntiles);
     else k_ord_count<16><<<ntiles, kOrdThreads, 0, c.stream>>>(s, n, shift, cnt, ntiles);
     launched();
-    size_t tb = 0;
-    NBG_HIP(rocprim::exclusive_scan(nullptr, tb, cnt, cnt, 0u, ncnt, rocprim::plus<uint32_t>(), c.stream));
-    c.ws_tmp.ensure(tb);
-    NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, cnt, cnt, 0u, ncnt, rocprim::plus<uint32_t>(), c.stream));
+    exclusive_scan_dev<uint32_t>(c, cnt, cnt, int64_t(ncnt));
     c.timing.launches++;
     if (items == 4)
       k_ord_scatter<4><<<ntiles, kOrdThreads, 0, c.stream>>>(s, idx, n, shift, cnt, ntiles, key_out, idx_out, decode,
@@ -469,10 +467,7 @@ struct OrderSort {
 };
 
 void scan_i64(Ctx& c, const int64_t* in, int64_t* out, int64_t n) {
-  size_t tb = 0;
-  NBG_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, int64_t(0), size_t(n), rocprim::plus<int64_t>(), c.stream));
-  c.ws_tmp.ensure(tb);
-  NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, in, out, int64_t(0), size_t(n), rocprim::plus<int64_t>(), c.stream));
+  exclusive_scan_dev<int64_t>(c, in, out, n);
   c.timing.launches++;
 }
 

@@ -149,12 +149,6 @@ struct SpBufs {
   int64_t cap_live[2], cap_arena, cap_meet, cap_sweep;
 };
 
-__device__ inline unsigned long long wsum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // wave-aggregated arr[key] += v over the lanes with act (lanes of one wave mostly share a key:
 // an edge tile covers consecutive frontier entries, usually of one pair).  Wave-uniform call.
 __device__ inline void wave_add_keyed(unsigned long long* arr, uint32_t key, unsigned long long v, bool act) {
@@ -164,7 +158,7 @@ __device__ inline void wave_add_keyed(unsigned long long* arr, uint32_t key, uns
     const int leader = __ffsll((long long)m) - 1;
     const uint32_t k = uint32_t(__shfl(int(key), leader));
     const bool mine = act && key == k;
-    const unsigned long long s = wsum(mine ? v : 0ull);
+    const unsigned long long s = wave_sum_u64(mine ? v : 0ull);
     if (lane == leader) atomicAdd(arr + k, s);
     m &= ~__ballot(mine);
     act = act && !mine;
@@ -427,7 +421,7 @@ __global__ __launch_bounds__(kBlk) void k_sp_select(const uint64_t* __restrict__
     esum += dsum;
   }
   __shared__ unsigned long long s_e[kBlk / 64];
-  const unsigned long long e = wsum(esum);
+  const unsigned long long e = wave_sum_u64(esum);
   if ((threadIdx.x & 63) == 0) s_e[threadIdx.x >> 6] = e;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -525,7 +519,7 @@ __global__ void k_sweep_push_select(const uint64_t* __restrict__ arena, int64_t 
         atomicOr(cnt + C_OVF, 2ull);
       }
     }
-    const unsigned long long e = wsum((unsigned long long)d);
+    const unsigned long long e = wave_sum_u64((unsigned long long)d);
     if ((threadIdx.x & 63) == 0 && e) atomicAdd(cnt + C_XE, e);
   }
 }
@@ -952,7 +946,7 @@ __global__ __launch_bounds__(256, OCC) void k_sp_probe(const uint64_t* __restric
   // one counter atomic per block: the grid's waves (up to 16 K) end together, and one add each
   // on the same counter queued behind each other at the kernel's tail
   __shared__ unsigned long long s_ev[4];
-  const unsigned long long ev = wsum(examined);
+  const unsigned long long ev = wave_sum_u64(examined);
   if (lane == 0) s_ev[threadIdx.x >> 6] = ev;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1027,7 +1021,7 @@ __global__ void k_sp_probe_end(SpState st, int32_t iter, const uint64_t* X, int6
       d = (unsigned long long)Xdeg[i];
       Xdeg[i] = 0;
     }
-    const unsigned long long sd = wsum(d);
+    const unsigned long long sd = wave_sum_u64(d);
     if ((threadIdx.x & 63) == 0 && sd) atomicAdd(cnt + C_XE, 0ull - sd);
   }
 }
@@ -1444,7 +1438,7 @@ __device__ inline void blk_reserve_n(unsigned long long* const* ctr, const uint3
 // one add per block of a per-thread value (kBlk threads, block-uniform call)
 __device__ inline void blk_add(unsigned long long* ctr, unsigned long long v) {
   __shared__ unsigned long long s_a[kBlk / 64];
-  v = wsum(v);
+  v = wave_sum_u64(v);
   if ((threadIdx.x & 63) == 0) s_a[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1605,7 +1599,7 @@ __global__ __launch_bounds__(256) void k_dv_begin(SpDev d, SpState st, SpCsr gou
     else atomicOr(gcnt(d.cnt, D_OVF), 2ull);
   }
   unsigned long long esum = go ? (unsigned long long)dg1 : 0ull;
-  esum = wsum(esum);
+  esum = wave_sum_u64(esum);
   if (lane == 0 && m) {
     atomicAdd(q1 + Q_X, (unsigned long long)__popcll(m));
     if (esum) atomicAdd(q1 + Q_XE, esum);
@@ -2064,7 +2058,7 @@ __global__ __launch_bounds__(256, OCC) void k_dv_expand(SpDev d, SpState st, SpF
           if (w0) atomicOr(row + lane, w0);
           if (w1) atomicOr(row + lane + 64, w1);
         }
-        dsum = wsum(dsum);
+        dsum = wave_sum_u64(dsum);
         if (lane == 0 && dsum) {
           atomicAdd(st.deg + side * B + p, dsum);
           // a forward level's (degree + 1) sum is also the sweep's push entries for that level
@@ -2413,7 +2407,7 @@ __global__ __launch_bounds__(256, OCC) void k_dv_sweep(SpDev d, SpState st, SpFi
             break;
           }
         }
-        pc = wsum(pc);
+        pc = wave_sum_u64(pc);
         if (lane == 0 && pc && pull_next) atomicAdd(pull_next + p, pc);
       });
   dv_flush_block(sg, d.cnt, q + Q_CLAIMS, out, d.cap_sw, d.arena, d.cap_arena);

@@ -12,8 +12,13 @@
 //   * && / || evaluate both sides; an error on either side is the result.
 #pragma once
 #include <cstdint>
+#include <string>
+#include <vector>
 
 namespace nbg {
+
+struct Field;        // engine.h
+struct TagFieldRef;  // engine.h
 
 enum VType : int32_t { VT_INT = 0, VT_DOUBLE = 1, VT_BOOL = 2, VT_STR = 3, VT_ERR = 4 };
 
@@ -61,5 +66,12 @@ struct FastPred {
   int32_t op = 0;     // REL op with the prop on the left
   int64_t k = 0;
 };
+
+// expr.cpp
+int32_t compile_expr(const uint8_t* buf, size_t len, const std::vector<Field>& fields, bool graphd,
+                     bool out_bound, Program* out, std::string* msg,
+                     const std::vector<TagFieldRef>* tags = nullptr, const std::vector<Field>* inputs = nullptr);
+Program program_dst();
+FastPred classify_pred(const Program& p, const std::vector<Field>& fields);
 
 }  // namespace nbg

@@ -23,6 +23,7 @@
 
 #include "device_common.h"
 #include "engine.h"
+#include "query_common.h"
 
 namespace nbg {
 
@@ -772,13 +773,6 @@ static int64_t unique_sorted(Ctx& c, T* in, T* out, int64_t n) {
   NBG_HIP(hipStreamSynchronize(c.stream));
   return int64_t(h);
 }
-template <typename T>
-static void exclusive_scan(Ctx& c, const T* in, T* out, int64_t n) {
-  size_t tb = 0;
-  NBG_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, T(0), size_t(n), rocprim::plus<T>(), c.stream));
-  c.ws_tmp.ensure(tb);
-  NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, in, out, T(0), size_t(n), rocprim::plus<T>(), c.stream));
-}
 
 // key transform for signed int64 sort order: flip the sign bit
 __global__ void k_flip_copy(const int64_t* in, uint64_t* out, int64_t n, int world, int parts, int rank,
@@ -1057,7 +1051,7 @@ static void gather_props(Ctx& c, Staging& s, const std::vector<Field>& fields, c
                                                              m, l2.as<int64_t>());
       NBG_HIP(hipMemsetAsync(l2.as<int64_t>() + m, 0, 8, c.stream));
       pc.str_off.alloc(size_t(m + 1) * 8);
-      exclusive_scan<int64_t>(c, l2.as<int64_t>(), pc.str_off.as<int64_t>(), m + 1);
+      exclusive_scan_dev<int64_t>(c, l2.as<int64_t>(), pc.str_off.as<int64_t>(), m + 1);
       int64_t total = 0;
       NBG_HIP(hipMemcpyAsync(&total, pc.str_off.as<int64_t>() + m, 8, hipMemcpyDeviceToHost, c.stream));
       NBG_HIP(hipStreamSynchronize(c.stream));
@@ -1267,10 +1261,7 @@ static void build_csr(Ctx& c, Staging& s, const std::vector<Field>& fields, bool
   DevBuf kept, cnt;
   kept.alloc(size_t(n) * 4);
   cnt.alloc(8);
-  size_t tb = 0;
-  NBG_HIP(rocprim::select(nullptr, tb, perm, keep.as<uint8_t>(), kept.as<uint32_t>(), cnt.as<uint64_t>(), size_t(n), c.stream));
-  c.ws_tmp.ensure(tb);
-  NBG_HIP(rocprim::select(c.ws_tmp.p, tb, perm, keep.as<uint8_t>(), kept.as<uint32_t>(), cnt.as<uint64_t>(), size_t(n), c.stream));
+  select_dev(c, perm, keep.as<uint8_t>(), kept.as<uint32_t>(), cnt.as<uint64_t>(), n);
   uint64_t m = 0;
   NBG_HIP(hipMemcpyAsync(&m, cnt.p, 8, hipMemcpyDeviceToHost, c.stream));
   NBG_HIP(hipStreamSynchronize(c.stream));
@@ -1301,18 +1292,8 @@ static void build_csr(Ctx& c, Staging& s, const std::vector<Field>& fields, bool
                                       rocprim::plus<uint32_t>(), c.stream));
       ovp.alloc(size_t(no) * 4 + 4);
       ove.alloc(size_t(no) * 4 + 4);
-      tb2 = 0;
-      NBG_HIP(rocprim::select(nullptr, tb2, perm, ovf.as<uint8_t>(), ovp.as<uint32_t>(), ocnt.as<uint64_t>(), size_t(n),
-                              c.stream));
-      c.ws_tmp.ensure(tb2);
-      NBG_HIP(rocprim::select(c.ws_tmp.p, tb2, perm, ovf.as<uint8_t>(), ovp.as<uint32_t>(), ocnt.as<uint64_t>(),
-                              size_t(n), c.stream));
-      tb2 = 0;
-      NBG_HIP(rocprim::select(nullptr, tb2, escan.as<uint32_t>(), ovf.as<uint8_t>(), ove.as<uint32_t>(),
-                              ocnt.as<uint64_t>(), size_t(n), c.stream));
-      c.ws_tmp.ensure(tb2);
-      NBG_HIP(rocprim::select(c.ws_tmp.p, tb2, escan.as<uint32_t>(), ovf.as<uint8_t>(), ove.as<uint32_t>(),
-                              ocnt.as<uint64_t>(), size_t(n), c.stream));
+      select_dev(c, perm, ovf.as<uint8_t>(), ovp.as<uint32_t>(), ocnt.as<uint64_t>(), n);
+      select_dev(c, escan.as<uint32_t>(), ovf.as<uint8_t>(), ove.as<uint32_t>(), ocnt.as<uint64_t>(), n);
       out.ov_n = int64_t(no);
       out.ov_edge.alloc(size_t(no) * 8 + 8);
       k_ov_edges<<<grid_for(int64_t(no)), 256, 0, c.stream>>>(ove.as<uint32_t>(), int64_t(no), out.ov_edge.as<int64_t>());
@@ -2067,7 +2048,7 @@ static void build_tag_columns(Ctx& c) {
           k_tag_str_len<<<grid_for(ng + 1), 256, 0, c.stream>>>(dwin.as<int32_t>(), ng, ts.stage.present[f].as<uint8_t>(),
                                                                  ts.stage.str_len[f].as<int64_t>(), lens.as<int64_t>());
         }
-        exclusive_scan<int64_t>(c, lens.as<int64_t>(), pc.str_off.as<int64_t>(), ng + 1);
+        exclusive_scan_dev<int64_t>(c, lens.as<int64_t>(), pc.str_off.as<int64_t>(), ng + 1);
         int64_t total = 0;
         NBG_HIP(hipMemcpyAsync(&total, pc.str_off.as<int64_t>() + ng, 8, hipMemcpyDeviceToHost, c.stream));
         NBG_HIP(hipStreamSynchronize(c.stream));
@@ -2079,7 +2060,7 @@ static void build_tag_columns(Ctx& c) {
         if (c.sharded) {
           // lengths of every rank's owned slice -> global offsets; bytes by owner block
           replicate_owned(c, lens, 8);
-          exclusive_scan<int64_t>(c, lens.as<int64_t>(), pc.str_off.as<int64_t>(), ng + 1);
+          exclusive_scan_dev<int64_t>(c, lens.as<int64_t>(), pc.str_off.as<int64_t>(), ng + 1);
           std::vector<int64_t> goff(size_t(ng) + 1);
           NBG_HIP(hipMemcpyAsync(goff.data(), pc.str_off.p, size_t(ng + 1) * 8, hipMemcpyDeviceToHost, c.stream));
           NBG_HIP(hipStreamSynchronize(c.stream));
@@ -2628,15 +2609,8 @@ static void finalize_rmat_stream(Ctx& c, EdgeSpace& es) {
   DevBuf idxA, idxB, cntb;
   idxA.alloc(size_t(NU) * 4);
   cntb.alloc(8);
-  {
-    size_t tb = 0;
-    rocprim::counting_iterator<uint32_t> it(0);
-    NBG_HIP(rocprim::select(nullptr, tb, it, present.as<uint8_t>(), idxA.as<uint32_t>(), cntb.as<uint64_t>(),
-                            size_t(NU), c.stream));
-    c.ws_tmp.ensure(tb);
-    NBG_HIP(rocprim::select(c.ws_tmp.p, tb, it, present.as<uint8_t>(), idxA.as<uint32_t>(), cntb.as<uint64_t>(),
-                            size_t(NU), c.stream));
-  }
+  select_dev(c, rocprim::counting_iterator<uint32_t>(0), present.as<uint8_t>(), idxA.as<uint32_t>(), cntb.as<uint64_t>(),
+             int64_t(NU));
   uint64_t hn = 0;
   NBG_HIP(hipMemcpyAsync(&hn, cntb.p, 8, hipMemcpyDeviceToHost, c.stream));
   NBG_HIP(hipStreamSynchronize(c.stream));
@@ -2729,7 +2703,7 @@ static void finalize_rmat_stream(Ctx& c, EdgeSpace& es) {
     out.n_rows = n_rows;
     DevBuf excl;
     excl.alloc(size_t(n_rows + 1) * 8);
-    exclusive_scan<int64_t>(c, (dir ? icnt : ocnt).as<int64_t>(), excl.as<int64_t>(), n_rows + 1);
+    exclusive_scan_dev<int64_t>(c, (dir ? icnt : ocnt).as<int64_t>(), excl.as<int64_t>(), n_rows + 1);
     int64_t total = 0;
     NBG_HIP(hipMemcpyAsync(&total, excl.as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost, c.stream));
     NBG_HIP(hipStreamSynchronize(c.stream));
@@ -2956,10 +2930,7 @@ void snapshot_finalize(Ctx& c) {
     sel.alloc(size_t(std::max<int64_t>(tot, 1)) * 8);
     cnt.alloc(8);
     k_owned_only<<<grid_for(tot), 256, 0, c.stream>>>(all.as<uint64_t>(), tot, c.num_parts, c.world, c.rank, flag.as<uint8_t>());
-    size_t tb = 0;
-    NBG_HIP(rocprim::select(nullptr, tb, all.as<uint64_t>(), flag.as<uint8_t>(), sel.as<uint64_t>(), cnt.as<uint64_t>(), size_t(tot), c.stream));
-    c.ws_tmp.ensure(tb);
-    NBG_HIP(rocprim::select(c.ws_tmp.p, tb, all.as<uint64_t>(), flag.as<uint8_t>(), sel.as<uint64_t>(), cnt.as<uint64_t>(), size_t(tot), c.stream));
+    select_dev(c, all.as<uint64_t>(), flag.as<uint8_t>(), sel.as<uint64_t>(), cnt.as<uint64_t>(), tot);
     uint64_t ns = 0;
     NBG_HIP(hipMemcpyAsync(&ns, cnt.p, 8, hipMemcpyDeviceToHost, c.stream));
     NBG_HIP(hipStreamSynchronize(c.stream));

@@ -14,13 +14,13 @@
 // binary search in LDS.  Consecutive lanes read consecutive adjacency entries, so the col /
 // prop loads of a tile are coalesced whatever the degree distribution (a supernode simply
 // spans many tiles).
+//
+// The kernels' expression VM is expr_device.h; storage getBound / boundStats is bound.hip.
 #include <chrono>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_reduce.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -30,359 +30,20 @@
 
 #include "device_common.h"
 #include "engine.h"
+#include "expr_device.h"
 #include "program.h"
+#include "query_common.h"
 #include "rows.h"
 
 namespace nbg {
-
-int32_t compile_expr(const uint8_t* buf, size_t len, const std::vector<Field>& fields, bool graphd,
-                     bool out_bound, Program* out, std::string* msg,
-                     const std::vector<TagFieldRef>* tags = nullptr, const std::vector<Field>* inputs = nullptr);
-Program program_dst();
-FastPred classify_pred(const Program& p, const std::vector<Field>& fields);
 
 constexpr int kThreads = 256;
 constexpr int kItems = 8;
 constexpr int kTile = kThreads * kItems;
 
-static int grid_cap(int64_t n, int block = 256, int cap = 256 * 16) {
-  int64_t g = (n + block - 1) / block;
-  return int(std::max<int64_t>(1, std::min<int64_t>(g, cap)));
-}
-
-// ------------------------------------------------------------------------------------------
-// device value model (boost::variant<int64,double,bool,string> + error)
-// ------------------------------------------------------------------------------------------
-struct Val {
-  int64_t b;
-  int32_t t;
-  int32_t len;
-};
-
-struct PropDev {
-  int32_t type;
-  int32_t width;
-  const void* data;
-  const uint8_t* present;
-  const int64_t* str_off;
-  const uint8_t* str_bytes;
-  const int32_t* part;  // tag columns: the part of each vertex's row (TagSpace::part)
-};
-struct EvalEnv {
-  const PropDev* props;  // device table, one entry per schema field (Csr::prop_table)
-  int32_t nprops;
-  int32_t etype;
-  const int64_t* vid_of;
-  const int32_t* col;
-  const int64_t* rank;
-  const PropDev* tprops;  // tag columns over the gidx space (Ctx::tag_refs order), or null
-  // $- / $var input table: open-addressing index src gidx -> its last input row, and columns
-  const int32_t* in_keys;
-  const int32_t* in_rows;
-  uint32_t in_mask;
-  const PropDev* iprops;
-  // STEPS > 1: root start (vid rank) of every final-frontier vertex and rank -> start gidx
-  const int32_t* in_root;
-  const int32_t* in_root_tab;
-  // storage (getBound) filters: a $^ tag row is visible when it sits in the request's part,
-  // which for an edge row is the part of the row's keys (Csr::row_part, local row = src - lo)
-  int32_t storage;
-  int64_t lo;
-  const int32_t* row_part;
-};
-__device__ inline uint32_t gidx_hash(int32_t g) { return uint32_t(g) * 2654435761u; }
-// row of the input table whose FROM vid is gidx g (-1: none)
-__device__ inline int32_t input_row(const EvalEnv& env, int32_t g) {
-  uint32_t h = gidx_hash(g) & env.in_mask;
-  for (uint32_t probe = 0; probe <= env.in_mask; probe++) {
-    const int32_t k = env.in_keys[h];
-    if (k == g) return env.in_rows[h];
-    if (k < 0) return -1;
-    h = (h + 1) & env.in_mask;
-  }
-  return -1;
-}
-
-__device__ inline int64_t load_int(const void* data, int width, int64_t i) {
-  switch (width) {
-    case 1: return int64_t(static_cast<const int8_t*>(data)[i]);
-    case 2: return int64_t(static_cast<const int16_t*>(data)[i]);
-    case 4: return int64_t(static_cast<const int32_t*>(data)[i]);
-    default: return static_cast<const int64_t*>(data)[i];
-  }
-}
-
-// compile-time width variant (W = 0: runtime width)
-template <int W>
-__device__ inline int64_t load_w(const void* data, int width, int64_t i) {
-  if (W == 1) return int64_t(static_cast<const int8_t*>(data)[i]);
-  if (W == 2) return int64_t(static_cast<const int16_t*>(data)[i]);
-  if (W == 4) return int64_t(static_cast<const int32_t*>(data)[i]);
-  if (W == 8) return static_cast<const int64_t*>(data)[i];
-  return load_int(data, width, i);
-}
-
-__device__ inline Val load_prop(const PropDev& p, int64_t ge) {
-  Val v;
-  v.len = 0;
-  if (p.present && !p.present[ge]) {
-    v.t = VT_ERR;
-    v.b = 0;
-    return v;
-  }
-  switch (p.type) {
-    case NBG_T_DOUBLE:
-    case NBG_T_FLOAT:
-      v.t = VT_DOUBLE;
-      v.b = static_cast<const int64_t*>(p.data)[ge];
-      break;
-    case NBG_T_BOOL:
-      v.t = VT_BOOL;
-      v.b = load_int(p.data, p.width, ge) != 0;
-      break;
-    case NBG_T_STRING: {
-      int64_t o = p.str_off[ge];
-      v.t = VT_STR;
-      v.b = int64_t(reinterpret_cast<uintptr_t>(p.str_bytes + o));
-      v.len = int32_t(p.str_off[ge + 1] - o);
-      break;
-    }
-    default:
-      v.t = VT_INT;
-      v.b = load_int(p.data, p.width, ge);
-  }
-  return v;
-}
-
-__device__ inline double as_d(const Val& v) { return v.t == VT_INT ? double(v.b) : __longlong_as_double(v.b); }
-__device__ inline bool as_bool(const Val& v) {
-  switch (v.t) {
-    case VT_INT: return v.b != 0;
-    case VT_DOUBLE: return __longlong_as_double(v.b) != 0.0;
-    case VT_BOOL: return v.b != 0;
-    default: return v.len == 0;  // string -> empty() (Expressions.h:172-173)
-  }
-}
-__device__ inline int str_cmp(const Val& a, const Val& b) {
-  const uint8_t* x = reinterpret_cast<const uint8_t*>(uintptr_t(a.b));
-  const uint8_t* y = reinterpret_cast<const uint8_t*>(uintptr_t(b.b));
-  int n = a.len < b.len ? a.len : b.len;
-  for (int i = 0; i < n; i++)
-    if (x[i] != y[i]) return x[i] < y[i] ? -1 : 1;
-  return a.len == b.len ? 0 : (a.len < b.len ? -1 : 1);
-}
-// boost::variant operator< : index first, then value
-__device__ inline bool v_lt(const Val& a, const Val& b) {
-  if (a.t != b.t) return a.t < b.t;
-  switch (a.t) {
-    case VT_INT: return a.b < b.b;
-    case VT_DOUBLE: return __longlong_as_double(a.b) < __longlong_as_double(b.b);
-    case VT_BOOL: return a.b < b.b;
-    default: return str_cmp(a, b) < 0;
-  }
-}
-__device__ inline bool v_eq(const Val& a, const Val& b) {
-  if (a.t != b.t) return false;
-  switch (a.t) {
-    case VT_INT:
-    case VT_BOOL: return a.b == b.b;
-    case VT_DOUBLE: return __longlong_as_double(a.b) == __longlong_as_double(b.b);
-    default: return str_cmp(a, b) == 0;
-  }
-}
-__device__ inline Val mk(int32_t t, int64_t b) {
-  Val v;
-  v.t = t;
-  v.b = b;
-  v.len = 0;
-  return v;
-}
-__device__ inline Val mkd(double d) { return mk(VT_DOUBLE, __double_as_longlong(d)); }
-
-__device__ Val eval_program(const Program* __restrict__ P, const EvalEnv& env, int64_t ge, int32_t src_g,
-                            int32_t dst_g) {
-  Val st[kMaxStack];
-  int sp = 0;
-  const int n = P->n;
-  for (int pc = 0; pc < n; pc++) {
-    Ins in = P->ins[pc];
-    switch (in.op) {
-      case P_CONST: {
-        Val v;
-        v.t = P->ctype[in.arg];
-        v.b = P->cbits[in.arg];
-        v.len = P->clen[in.arg];
-        if (v.t == VT_STR) v.b = int64_t(reinterpret_cast<uintptr_t>(P->cstr + P->cbits[in.arg]));
-        st[sp++] = v;
-        break;
-      }
-      case P_PROP: st[sp++] = load_prop(env.props[in.arg], ge); break;
-      case P_DST: st[sp++] = mk(VT_INT, env.vid_of[dst_g]); break;
-      case P_SRC: st[sp++] = mk(VT_INT, env.vid_of[src_g]); break;
-      case P_RANK: st[sp++] = mk(VT_INT, env.rank ? env.rank[ge] : 0); break;
-      case P_TYPE: st[sp++] = mk(VT_INT, env.etype); break;
-      case P_SRCTAG:
-      case P_DSTTAG: {
-        // only a row of the vertex's own part is visible to GO (presence byte 1; 2 = a row that
-        // only a getBound naming its foreign part reads)
-        const PropDev& tp = env.tprops[in.arg];
-        const int32_t g = in.op == P_SRCTAG ? src_g : dst_g;
-        const bool vis = env.storage ? tp.present[g] != 0 && tp.part[g] == env.row_part[src_g - env.lo]
-                                     : tp.present[g] == 1;
-        st[sp++] = vis ? load_prop(tp, g) : mk(VT_ERR, 0);
-        break;
-      }
-      case P_INPUT: {
-        int32_t g0 = src_g;
-        if (env.in_root) {  // multi-step: the input row of the vertex's root start
-          const int32_t r = env.in_root[src_g];
-          g0 = r == INT32_MAX ? -1 : env.in_root_tab[r];
-        }
-        const int32_t row = g0 < 0 ? -1 : input_row(env, g0);
-        st[sp++] = row < 0 ? mk(VT_ERR, 0) : load_prop(env.iprops[in.arg], row);
-        break;
-      }
-      case P_UNARY: {
-        Val& a = st[sp - 1];
-        if (a.t == VT_ERR) break;
-        if (in.sub == 0) break;  // PLUS
-        if (in.sub == 1) {       // NEGATE
-          if (a.t == VT_INT) a.b = int64_t(0ull - uint64_t(a.b));
-          else if (a.t == VT_DOUBLE) a.b = __double_as_longlong(-__longlong_as_double(a.b));
-          else a.t = VT_ERR;
-        } else {
-          a = mk(VT_BOOL, !as_bool(a));
-        }
-        break;
-      }
-      case P_ARITH: {
-        Val r = st[--sp];
-        Val l = st[sp - 1];
-        Val o;
-        if (l.t == VT_ERR) o = l;
-        else if (r.t == VT_ERR) o = r;
-        else {
-          bool ar = (l.t == VT_INT || l.t == VT_DOUBLE) && (r.t == VT_INT || r.t == VT_DOUBLE);
-          bool dbl = l.t == VT_DOUBLE || r.t == VT_DOUBLE;
-          o = mk(VT_ERR, 0);
-          switch (in.sub) {
-            case 0:
-              if (ar) o = dbl ? mkd(as_d(l) + as_d(r)) : mk(VT_INT, int64_t(uint64_t(l.b) + uint64_t(r.b)));
-              break;
-            case 1:
-              if (ar) o = dbl ? mkd(as_d(l) - as_d(r)) : mk(VT_INT, int64_t(uint64_t(l.b) - uint64_t(r.b)));
-              break;
-            case 2:
-              if (ar) o = dbl ? mkd(as_d(l) * as_d(r)) : mk(VT_INT, int64_t(uint64_t(l.b) * uint64_t(r.b)));
-              break;
-            case 3:
-              if (ar) {
-                if (dbl) o = mkd(as_d(l) / as_d(r));
-                else if (r.b == 0) o = mk(VT_ERR, 0);
-                else if (r.b == -1) o = mk(VT_INT, int64_t(0ull - uint64_t(l.b)));
-                else o = mk(VT_INT, l.b / r.b);
-              }
-              break;
-            default:
-              if (l.t == VT_INT && r.t == VT_INT) {
-                if (r.b == 0) o = mk(VT_ERR, 0);
-                else if (r.b == -1) o = mk(VT_INT, 0);
-                else o = mk(VT_INT, l.b % r.b);
-              }
-          }
-        }
-        st[sp - 1] = o;
-        break;
-      }
-      case P_REL: {
-        Val r = st[--sp];
-        Val l = st[sp - 1];
-        Val o;
-        if (l.t == VT_ERR) o = l;
-        else if (r.t == VT_ERR) o = r;
-        else {
-          bool res;
-          bool mixed = (l.t == VT_INT || l.t == VT_DOUBLE) && (r.t == VT_INT || r.t == VT_DOUBLE) &&
-                       (l.t == VT_DOUBLE || r.t == VT_DOUBLE);
-          switch (in.sub) {
-            case 0: res = v_lt(l, r); break;
-            case 1: res = !v_lt(r, l); break;
-            case 2: res = v_lt(r, l); break;
-            case 3: res = !v_lt(l, r); break;
-            case 4: res = mixed ? fabs(as_d(l) - as_d(r)) < 1e-8 : v_eq(l, r); break;
-            default: res = mixed ? !(fabs(as_d(l) - as_d(r)) < 1e-8) : !v_eq(l, r); break;
-          }
-          o = mk(VT_BOOL, res);
-        }
-        st[sp - 1] = o;
-        break;
-      }
-      case P_LOGIC: {
-        Val r = st[--sp];
-        Val l = st[sp - 1];
-        Val o;
-        if (l.t == VT_ERR) o = l;
-        else if (r.t == VT_ERR) o = r;
-        else if (in.sub == 0) o = mk(VT_BOOL, as_bool(l) ? as_bool(r) : false);
-        else o = mk(VT_BOOL, as_bool(l) ? true : as_bool(r));
-        st[sp - 1] = o;
-        break;
-      }
-    }
-  }
-  return st[0];
-}
-
 // ------------------------------------------------------------------------------------------
 // expansion
 // ------------------------------------------------------------------------------------------
-enum ExpMode : int { EXP_MARK = 0, EXP_ROWS = 1, EXP_FLAGS = 2 };
-enum PredKind : int { PK_NONE = 0, PK_FAST = 1, PK_VM = 2 };
-
-struct ExpandArgs {
-  const int32_t* F;
-  int64_t nF;
-  const int64_t* off;      // exclusive degree scan, off[nF] = total edges
-  const int64_t* row_ptr;
-  const int32_t* col;
-  int64_t lo;              // gidx of local row 0
-  uint8_t* map;            // EXP_MARK
-  int32_t* rows_src;       // EXP_ROWS: local row index
-  int64_t* rows_edge;      //           global edge index into the CSR
-  unsigned long long* rows_cnt;
-  uint8_t* flags;          // EXP_FLAGS: one byte per flattened edge slot
-  unsigned long long* err; // eval errors (GO semantics)
-  int32_t storage;         // 1: eval error keeps the edge (QueryBaseProcessor.inl:391-396)
-  int32_t mark_check;      // read the byte before storing it
-  int64_t* out_vid;        // EXP_ROWS fused YIELD _dst: write vid_of[dst] instead of (src, edge)
-  const int64_t* vid_of;
-  const int64_t* col_vid;  // per-edge dst vid (Csr::col_vid) or null: vid_of[col[e]]
-  const int32_t* tile_row; // [ntiles + 1]: frontier entry holding the first slot of each tile
-                           // (k_tile_rows), or null: binary search of off[]
-  // multi-step $- / $var (VertexBackTracker, GoExecutor.h:174-193): root start of every marked
-  // dst = the smallest (by vid rank) root of its in-edges' srcs this hop, or null
-  const int32_t* root_cur;
-  int32_t* root_next;
-};
-struct FastArgs {
-  const void* data;
-  const uint8_t* present;
-  int32_t width;
-  int32_t op;
-  int64_t k;
-};
-
-__host__ __device__ inline bool fast_cmp(int op, int64_t a, int64_t k) {
-  switch (op) {
-    case 0: return a < k;
-    case 1: return a <= k;
-    case 2: return a > k;
-    case 3: return a >= k;
-    case 4: return a == k;
-    default: return a != k;
-  }
-}
-
 // Quantised predicate on packed bottom-up words (EdgeSpace::q_*): the low gbits bits are the
 // source gidx, the bits above the bucket of the predicate column's value.  The compare decides
 // every bucket below ulo (`below`: 1 pass, 0 fail) and above uhi (`above`); buckets in
@@ -416,12 +77,6 @@ __device__ inline int q_test(int32_t s, const QArgs& q) {
   r = b > q.uhi ? q.above : r;
   r = b < q.ulo ? q.below : r;
   return r;
-}
-
-// raw buffer resource over p (gfx9 word 3; bounds left to the caller): loads through it are
-// buffer instructions, which the compiler never merges with LDS reads into a flat load
-__device__ inline __amdgpu_buffer_rsrc_t raw_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
 }
 
 template <int MODE, int PK>
@@ -641,12 +296,6 @@ __device__ inline uint32_t wave_excl_scan(uint32_t x, uint32_t& total) {
   }
   total = __shfl(v, 63);
   return v - x;
-}
-
-__device__ inline unsigned long long wave_sum_u64(unsigned long long x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
 }
 
 // ---- block-level aggregation helpers (one atomic per block or none: a single global counter
@@ -2377,28 +2026,23 @@ __global__ void k_root_init(const int32_t* sg, const int32_t* srank, int64_t n, 
 // ------------------------------------------------------------------------------------------
 // host drivers
 // ------------------------------------------------------------------------------------------
-namespace {
-
 EvalEnv make_env(Ctx& c, EdgeSpace& es, Csr& csr, int32_t etype) {
   EvalEnv env{};
   env.nprops = int32_t(csr.props.size());
+  auto upload = [](DevBuf& d, const std::vector<PropDev>& tab) {
+    d.alloc(sizeof(PropDev) * tab.size());
+    NBG_HIP(hipMemcpy(d.p, tab.data(), sizeof(PropDev) * tab.size(), hipMemcpyHostToDevice));
+  };
   if (env.nprops && !csr.prop_table.p) {
     std::vector<PropDev> tab;
-    for (const PropCol& p : csr.props)
-      tab.push_back(PropDev{p.type, p.width, p.data.p, p.present.as<uint8_t>(), p.str_off.as<int64_t>(),
-                            p.str_bytes.as<uint8_t>()});
-    csr.prop_table.alloc(sizeof(PropDev) * tab.size());
-    NBG_HIP(hipMemcpy(csr.prop_table.p, tab.data(), sizeof(PropDev) * tab.size(), hipMemcpyHostToDevice));
+    append_prop_devs(tab, csr.props);
+    upload(csr.prop_table, tab);
   }
   env.props = csr.prop_table.as<PropDev>();
   if (!c.tag_refs.empty() && !c.tag_table.p) {
     std::vector<PropDev> tab;
-    for (auto& kv : c.tags)
-      for (const PropCol& p : kv.second.cols)
-        tab.push_back(PropDev{p.type, p.width, p.data.p, p.present.as<uint8_t>(), p.str_off.as<int64_t>(),
-                              p.str_bytes.as<uint8_t>(), kv.second.part.as<int32_t>()});
-    c.tag_table.alloc(sizeof(PropDev) * tab.size());
-    NBG_HIP(hipMemcpy(c.tag_table.p, tab.data(), sizeof(PropDev) * tab.size(), hipMemcpyHostToDevice));
+    for (auto& kv : c.tags) append_prop_devs(tab, kv.second.cols, kv.second.part.as<int32_t>());
+    upload(c.tag_table, tab);
   }
   env.tprops = c.tag_table.as<PropDev>();
   env.etype = etype;
@@ -2408,23 +2052,7 @@ EvalEnv make_env(Ctx& c, EdgeSpace& es, Csr& csr, int32_t etype) {
   return env;
 }
 
-template <typename T>
-void exclusive_scan_dev(Ctx& c, const T* in, T* out, int64_t n) {
-  size_t tb = 0;
-  NBG_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, T(0), size_t(n), rocprim::plus<T>(), c.stream));
-  c.ws_tmp.ensure(tb);
-  NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, in, out, T(0), size_t(n), rocprim::plus<T>(), c.stream));
-}
-
-// rocprim::select in its two calls (size query, run): in[i] with flags[i] != 0 to out, in order;
-// their count to *cnt (device)
-template <typename In, typename Flags, typename Out>
-void select_dev(Ctx& c, In in, Flags flags, Out out, uint64_t* cnt, int64_t n) {
-  size_t tb = 0;
-  NBG_HIP(rocprim::select(nullptr, tb, in, flags, out, cnt, size_t(n), c.stream));
-  c.ws_tmp.ensure(tb);
-  NBG_HIP(rocprim::select(c.ws_tmp.p, tb, in, flags, out, cnt, size_t(n), c.stream));
-}
+namespace {
 
 // a query's counter block (CounterWord / SpecWord index both)
 struct Counters {
@@ -3186,24 +2814,10 @@ uint64_t bu_first_bytes(const unsigned long long* h, int64_t n_rows, uint64_t od
 uint64_t bu_rest_bytes(const unsigned long long* h, int pred_width, bool rec) {
   return h[kHopPending] * (rec ? 64 : 16) + h[kHopEntries] * 4 + h[kHopValues] * uint64_t(pred_width);
 }
-// algorithmic bytes of one expansion (DESIGN.md "byte model"): frontier id 4 B + row_ptr pair
-// 16 B + off 8 B per frontier entry; per edge: col 4 B (+ predicate column width) + the
-// output it makes (1 B map mark, or 12 B row, or 1 B flag).
-uint64_t expand_bytes(int64_t nF, int64_t E, int pred_width, int mode) {
-  uint64_t b = uint64_t(nF) * 28 + uint64_t(E) * (4 + uint64_t(pred_width));
-  b += uint64_t(E) * (mode == EXP_ROWS ? 0 : 1);
-  return b;
-}
 
 // a lone YIELD _dst (also the default YIELD): no YIELD program runs, the rows are dst vids
 bool is_lone_dst(const std::vector<Program>& yields) {
   return yields.size() == 1 && yields[0].n == 1 && yields[0].ins[0].op == P_DST;
-}
-// a PK_FAST predicate's typed compare on the CSR's own column (else: no arguments)
-FastArgs fast_args(const Csr& csr, const FastPred& fpk) {
-  if (fpk.kind != PK_FAST) return FastArgs{};
-  const PropCol& pc = csr.props[size_t(fpk.col)];
-  return FastArgs{pc.data.p, pc.present.as<uint8_t>(), pc.width, fpk.op, fpk.k};
 }
 // the predicate can run bottom-up: only when it cannot error (the reference fails the query on
 // any row's eval error, so every row must be evaluated when errors are possible) -- none, or a
@@ -3216,12 +2830,31 @@ bool pred_runs_bottom_up(const FastPred& fpk, const FastArgs& fp, const EdgeSpac
 int32_t result_type(int32_t vt) {
   return vt == VT_DOUBLE ? NBG_T_DOUBLE : vt == VT_BOOL ? NBG_T_BOOL : vt == VT_STR ? NBG_T_STRING : NBG_T_VID;
 }
+
+}  // namespace
+
+// ---- called from bound.hip too (query_common.h) ----
+void expand_flags(Ctx& c, ExpandArgs a, int pk, const FastArgs& fp, const Program* dprog, const EvalEnv& env, int64_t E) {
+  launch_expand<EXP_FLAGS>(c, a, pk, fp, dprog, env, E);
+}
+// algorithmic bytes of one expansion (DESIGN.md "byte model"): frontier id 4 B + row_ptr pair
+// 16 B + off 8 B per frontier entry; per edge: col 4 B (+ predicate column width) + the
+// output it makes (1 B map mark, or 12 B row, or 1 B flag).
+uint64_t expand_bytes(int64_t nF, int64_t E, int pred_width, int mode) {
+  uint64_t b = uint64_t(nF) * 28 + uint64_t(E) * (4 + uint64_t(pred_width));
+  b += uint64_t(E) * (mode == EXP_ROWS ? 0 : 1);
+  return b;
+}
+// a PK_FAST predicate's typed compare on the CSR's own column (else: no arguments)
+FastArgs fast_args(const Csr& csr, const FastPred& fpk) {
+  if (fpk.kind != PK_FAST) return FastArgs{};
+  const PropCol& pc = csr.props[size_t(fpk.col)];
+  return FastArgs{pc.data.p, pc.present.as<uint8_t>(), pc.width, fpk.op, fpk.k};
+}
 // the type a stored column is returned as: FLOAT widens to DOUBLE, VID and TIMESTAMP are INTs
 int32_t column_result_type(int32_t t) {
   return t == NBG_T_FLOAT ? NBG_T_DOUBLE : (t == NBG_T_VID || t == NBG_T_TIMESTAMP) ? NBG_T_INT : t;
 }
-
-}  // namespace
 
 // once per snapshot (collective): the out-edges summed over ranks, the largest out-degree and
 // the prefix sums of the kTopDeg largest out-degrees over ranks, so that every rank takes the
@@ -4636,768 +4269,6 @@ void timing_resolve(Ctx& c) {
     }
   }
   timing_reset(c);
-}
-
-// ------------------------------------------------------------------------------------------
-// getBound (QueryBoundProcessor)
-// ------------------------------------------------------------------------------------------
-// request entry -> local row; a (part, vid) pair whose part does not hold the vertex's keys scans
-// an empty prefix in the reference, so it gets a zero-degree stand-in (-1)
-__global__ void k_bound_frontier(const int32_t* parts, const int32_t* g, int64_t n, int64_t lo, int64_t hi,
-                                 const int32_t* row_part, int32_t* F) {
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) {
-    int32_t x = g[i];
-    bool ok = x >= lo && x < hi && row_part[x - lo] == parts[i];
-    F[i] = ok ? int32_t(x - lo) : -1;
-  }
-}
-__global__ void k_degrees_masked(const int32_t* F, int64_t n, const int64_t* row_ptr, int64_t* deg) {
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i <= n; i += int64_t(gridDim.x) * blockDim.x) {
-    if (i == n) deg[i] = 0;
-    else deg[i] = F[i] < 0 ? 0 : row_ptr[F[i] + 1] - row_ptr[F[i]];
-  }
-}
-// request entries with deg 0 are removed so every frontier entry covers >= 1 edge slot
-__global__ void k_slot_owner(const int64_t* kept_slots, int64_t m, const int64_t* off, int64_t nF, int64_t* owner) {
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < m; i += int64_t(gridDim.x) * blockDim.x) {
-    int64_t e = kept_slots[i];
-    int64_t lo = 0, hi = nF;
-    while (hi - lo > 1) {
-      int64_t mid = (lo + hi) >> 1;
-      if (off[mid] <= e) lo = mid; else hi = mid;
-    }
-    owner[i] = lo;
-  }
-}
-struct BoundCol {
-  int32_t kind;  // 0 prop, 1 _dst, 2 _src, 3 _rank, 4 _type
-  int32_t prop;
-  int32_t type;  // NBG_T_*
-  int32_t stat;  // outBoundStats: cpp2::StatType SUM 1 / COUNT 2 / AVG 3 (0: plain getBound)
-  void* out;
-  int64_t* str_len;  // STRING pass 1
-};
-constexpr int kMaxBoundCols = 32;
-struct BoundCols {
-  int32_t n;
-  BoundCol c[kMaxBoundCols];
-};
-// flattened slot -> edge index of the kept rows
-__global__ void k_slot_ge(const int64_t* kept_slots, const int64_t* owner, int64_t m, const int64_t* off,
-                          const int32_t* F, const int64_t* row_ptr, int64_t* ge) {
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < m; i += int64_t(gridDim.x) * blockDim.x) {
-    const int64_t k = owner[i];
-    ge[i] = row_ptr[F[k]] + (kept_slots[i] - off[k]);
-  }
-}
-// one value of a getBound column for row i: edge ge's key props, and its props either from the
-// CSR (old < 0) or from the older-version side table (row old, Csr::ov_*)
-__device__ inline int64_t bound_value(const BoundCol& b, int64_t ge, int64_t old, int32_t f, int64_t lo,
-                                      const EvalEnv& env, const PropDev* oprops, bool& present) {
-  present = true;
-  switch (b.kind) {
-    case 1: return env.vid_of[env.col[ge]];
-    case 2: return env.vid_of[lo + f];
-    case 3: return env.rank ? env.rank[ge] : 0;
-    case 4: return env.etype;
-    default: {
-      const PropDev& p = old < 0 ? env.props[b.prop] : oprops[b.prop];
-      const int64_t x = old < 0 ? ge : old;
-      if (p.present && !p.present[x]) {
-        present = false;
-        return INT64_MIN;
-      }
-      if (p.type == NBG_T_STRING) return x;
-      if (p.type == NBG_T_DOUBLE || p.type == NBG_T_FLOAT) return static_cast<const int64_t*>(p.data)[x];
-      return load_int(p.data, p.width, x);
-    }
-  }
-}
-__global__ void k_bound_rows(const int64_t* ge_in, const int64_t* old_in, const int64_t* owner, int64_t m,
-                             const int32_t* F, int64_t lo, EvalEnv env, const PropDev* oprops, BoundCols bc) {
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < m; i += int64_t(gridDim.x) * blockDim.x) {
-    const int64_t ge = ge_in[i];
-    const int64_t old = old_in ? old_in[i] : -1;
-    const int32_t f = F[owner[i]];
-    for (int c = 0; c < bc.n; c++) {
-      const BoundCol& b = bc.c[c];
-      bool present;
-      const int64_t v = bound_value(b, ge, old, f, lo, env, oprops, present);
-      if (b.kind == 0) {
-        const PropDev& p = old < 0 ? env.props[b.prop] : oprops[b.prop];
-        if (p.type == NBG_T_STRING) {
-          b.str_len[i] = present ? p.str_off[v + 1] - p.str_off[v] : -1;
-          continue;
-        }
-      }
-      if (b.type == NBG_T_BOOL) static_cast<uint8_t*>(b.out)[i] = uint8_t(v != 0);
-      else static_cast<int64_t*>(b.out)[i] = v;
-    }
-  }
-}
-// outBoundStats / inBoundStats (QueryStatsProcessor.cpp:69-125, StatsCollector Collector.h:66-94):
-// over the kept rows, the int64 sum (wrapping, as the reference's int64 adds) and the count of
-// present values of column c.  acc[2c] = sum, acc[2c+1] = count.  Doubles only count (a double
-// reaching the reference's int64-initialised sum throws, reported by the caller).
-__global__ void k_bound_stats(const int64_t* ge_in, const int64_t* old_in, const int64_t* owner, int64_t m,
-                              const int32_t* F, int64_t lo, EvalEnv env, const PropDev* oprops, BoundCol b,
-                              unsigned long long* acc) {
-  unsigned long long sum = 0, cnt = 0;
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < m; i += int64_t(gridDim.x) * blockDim.x) {
-    const int64_t old = old_in ? old_in[i] : -1;
-    bool present;
-    int64_t v = bound_value(b, ge_in[i], old, F[owner[i]], lo, env, oprops, present);
-    if (b.kind == 0) {
-      const int32_t t = (old < 0 ? env.props[b.prop] : oprops[b.prop]).type;
-      if (t == NBG_T_STRING || t == NBG_T_DOUBLE || t == NBG_T_FLOAT || t == NBG_T_BOOL) v = 0;
-    }
-    if (present) {
-      sum += (unsigned long long)v;
-      cnt++;
-    }
-  }
-  sum = wave_sum_u64(sum);
-  cnt = wave_sum_u64(cnt);
-  if ((threadIdx.x & 63) == 0 && cnt) {
-    atomicAdd(acc, sum);
-    atomicAdd(acc + 1, cnt);
-  }
-}
-
-// collectEdgeProps' firstLoop (QueryBaseProcessor.inl:349-402): until a key is emitted the scan
-// does not skip a group's older versions, so when every key before it fails the filter (all
-// versions of the earlier groups and the newer versions of its own group), the first older
-// version that passes is emitted, ahead of the row's ordinary rows.  One thread per request
-// entry (frontier entry k = local row F[k], flags of its edges at off[k]..): walks its edges in
-// key order until the first kept one; per edge whose first version failed, its older versions.
-// x_old[k] = the emitted older version's side-table row (-1: none), x_ge[k] = its edge.
-template <int PK>
-__global__ void k_first_loop(const int32_t* F, const int64_t* off, int64_t nF, const int64_t* row_ptr,
-                             const uint8_t* flags, const int64_t* ov_edge, int64_t ov_n, const Program* prog,
-                             EvalEnv oenv, FastArgs ofp, int64_t lo, int64_t* x_old, int64_t* x_ge) {
-  for (int64_t k = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; k < nF; k += int64_t(gridDim.x) * blockDim.x) {
-    x_old[k] = -1;
-    const int32_t f = F[k];
-    const int64_t b = row_ptr[f], e = row_ptr[f + 1];
-    int64_t l = 0, h = ov_n;  // first older version at or after edge b
-    while (l < h) {
-      const int64_t mid = (l + h) >> 1;
-      if (ov_edge[mid] < b) l = mid + 1; else h = mid;
-    }
-    int64_t x = b;  // edges [b, x) checked: their first versions failed
-    for (int64_t o = l; o < ov_n && ov_edge[o] < e;) {
-      const int64_t ge = ov_edge[o];
-      bool kept = false;
-      for (; x <= ge && !kept; x++) kept = flags[off[k] + (x - b)] != 0;
-      if (kept) break;  // an ordinary row comes first: firstLoop ends there
-      bool hit = false;
-      for (; o < ov_n && ov_edge[o] == ge && !hit; o++) {
-        bool pass;
-        if (PK == PK_FAST) {
-          pass = (ofp.present && !ofp.present[o]) ? true
-                                                   : fast_cmp(ofp.op, static_cast<const int64_t*>(ofp.data)[o], ofp.k);
-        } else {
-          const Val v = eval_program(prog, oenv, o, int32_t(lo) + f, 0);
-          pass = v.t == VT_ERR ? true : as_bool(v);  // storage: an eval error keeps the edge
-        }
-        if (pass) {
-          x_old[k] = o;
-          x_ge[k] = ge;
-          hit = true;
-        }
-      }
-      if (hit) break;
-    }
-  }
-}
-// merged row list: entry k's older-version row (if any) goes first, then its kept rows.
-// cx = inclusive count of entries with an older-version row.
-__global__ void k_merge_kept(const int64_t* ge, const int64_t* owner, int64_t m, const int64_t* cx, int64_t* mge,
-                             int64_t* mold, int64_t* mowner) {
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < m; i += int64_t(gridDim.x) * blockDim.x) {
-    const int64_t k = owner[i];
-    const int64_t pos = i + cx[k];
-    mge[pos] = ge[i];
-    mold[pos] = -1;
-    mowner[pos] = k;
-  }
-}
-__global__ void k_merge_old(const int64_t* x_old, const int64_t* x_ge, int64_t nF, const int64_t* owner, int64_t m,
-                            const int64_t* cx, int64_t* mge, int64_t* mold, int64_t* mowner) {
-  for (int64_t k = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; k < nF; k += int64_t(gridDim.x) * blockDim.x) {
-    if (x_old[k] < 0) continue;
-    int64_t l = 0, h = m;  // kept rows of entries < k
-    while (l < h) {
-      const int64_t mid = (l + h) >> 1;
-      if (owner[mid] < k) l = mid + 1; else h = mid;
-    }
-    const int64_t pos = l + cx[k] - 1;
-    mge[pos] = x_ge[k];
-    mold[pos] = x_old[k];
-    mowner[pos] = k;
-  }
-}
-
-__global__ void k_str_gather(const int64_t* ge, const int64_t* old, int64_t m, const int64_t* src_off,
-                             const uint8_t* src_bytes, const int64_t* osrc_off, const uint8_t* osrc_bytes,
-                             const int64_t* dst_off, uint8_t* dst) {
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < m; i += int64_t(gridDim.x) * blockDim.x) {
-    int64_t len = dst_off[i + 1] - dst_off[i];
-    const bool o = old && old[i] >= 0;
-    const uint8_t* s = o ? osrc_bytes + osrc_off[old[i]] : src_bytes + src_off[ge[i]];
-    for (int64_t j = 0; j < len; j++) dst[dst_off[i] + j] = s[j];
-  }
-}
-__global__ void k_clamp_len(int64_t* l, int64_t m) {
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < m; i += int64_t(gridDim.x) * blockDim.x)
-    if (l[i] < 0) l[i] = 0;
-}
-
-// tag column values of the returned vertices (gidx list): value bits, presence state, part, and
-// STRING (offset, length) into the column's bytes
-__global__ void k_tag_fetch(const int32_t* g, int64_t m, const int64_t* data, const uint8_t* present,
-                            const int32_t* tpart, const int64_t* str_off, int64_t* val, uint8_t* state,
-                            int32_t* part, int64_t* soff, int64_t* slen) {
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < m; i += int64_t(gridDim.x) * blockDim.x) {
-    const int32_t x = g[i];
-    const bool ok = x >= 0;
-    val[i] = ok ? data[x] : 0;
-    state[i] = ok ? present[x] : 0;
-    part[i] = ok ? tpart[x] : -1;
-    if (str_off) {
-      soff[i] = ok ? str_off[x] : 0;
-      slen[i] = ok ? str_off[x + 1] - str_off[x] : 0;
-    }
-  }
-}
-__global__ void k_bytes_gather(const int64_t* soff, const int64_t* doff, int64_t m, const uint8_t* src, uint8_t* dst) {
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < m; i += int64_t(gridDim.x) * blockDim.x)
-    for (int64_t j = 0; j < doff[i + 1] - doff[i]; j++) dst[doff[i] + j] = src[soff[i] + j];
-}
-
-// Fills h->vertex_* for the returned vertices (h->vertex_ids, request parts vparts): a value is
-// visible when the vertex's row sits in the request's part -- collectVertexProps scans
-// prefix(request part, vid, tag) (QueryBaseProcessor.inl:309-333) -- else absent (the reference
-// then skips the prop in the vertex row, RowWriter without it).
-template <typename F>
-void fetch_vertex_tags(Ctx& c, HostRows* h, const std::vector<int32_t>& vparts, F col_of, size_t ncols) {
-  const int64_t nv = int64_t(h->vertex_ids.size());
-  DevBuf dv, dg, val, stt, prt, soff, slen;
-  const size_t cap = size_t(std::max<int64_t>(nv, 1));
-  dv.alloc(cap * 8);
-  dg.alloc(cap * 4);
-  val.alloc(cap * 8);
-  stt.alloc(cap);
-  prt.alloc(cap * 4);
-  soff.alloc(cap * 8);
-  slen.alloc(cap * 8);
-  if (nv) {
-    NBG_HIP(hipMemcpyAsync(dv.p, h->vertex_ids.data(), size_t(nv) * 8, hipMemcpyHostToDevice, c.stream));
-    lookup_gidx(c, dv.as<int64_t>(), dg.as<int32_t>(), nv);
-  }
-  for (size_t t = 0; t < ncols; t++) {
-    const auto tf = col_of(t);
-    const TagSpace& ts = *tf.first;
-    const PropCol& pc = ts.cols[tf.second];
-    const bool is_str = pc.type == NBG_T_STRING;
-    std::vector<int64_t> hv(cap), hoff(cap), hlen(cap);
-    std::vector<uint8_t> hs(cap);
-    std::vector<int32_t> hp(cap);
-    if (nv) {
-      k_tag_fetch<<<grid_cap(nv), 256, 0, c.stream>>>(dg.as<int32_t>(), nv, pc.data.as<int64_t>(), pc.present.as<uint8_t>(),
-                                                      ts.part.as<int32_t>(), is_str ? pc.str_off.as<int64_t>() : nullptr,
-                                                      val.as<int64_t>(), stt.as<uint8_t>(), prt.as<int32_t>(),
-                                                      soff.as<int64_t>(), slen.as<int64_t>());
-      NBG_HIP(hipGetLastError());
-      NBG_HIP(hipMemcpyAsync(hv.data(), val.p, size_t(nv) * 8, hipMemcpyDeviceToHost, c.stream));
-      NBG_HIP(hipMemcpyAsync(hs.data(), stt.p, size_t(nv), hipMemcpyDeviceToHost, c.stream));
-      NBG_HIP(hipMemcpyAsync(hp.data(), prt.p, size_t(nv) * 4, hipMemcpyDeviceToHost, c.stream));
-      if (is_str) {
-        NBG_HIP(hipMemcpyAsync(hoff.data(), soff.p, size_t(nv) * 8, hipMemcpyDeviceToHost, c.stream));
-        NBG_HIP(hipMemcpyAsync(hlen.data(), slen.p, size_t(nv) * 8, hipMemcpyDeviceToHost, c.stream));
-      }
-      NBG_HIP(hipStreamSynchronize(c.stream));
-    }
-    std::vector<uint8_t> pres(cap, 0);
-    for (int64_t i = 0; i < nv; i++) {
-      const int32_t rp = vparts[size_t(i)];
-      const bool own = hs[size_t(i)] == 1 && rp == part_of_vid(h->vertex_ids[size_t(i)], c.num_parts);
-      const bool foreign = hs[size_t(i)] == 2 && rp == hp[size_t(i)];
-      pres[size_t(i)] = own || foreign;
-    }
-    h->vertex_types.push_back(column_result_type(pc.type));
-    h->vertex_present.push_back(pres);
-    if (is_str) {
-      std::vector<int64_t> offs(size_t(nv) + 1, 0);
-      for (int64_t i = 0; i < nv; i++) offs[size_t(i + 1)] = offs[size_t(i)] + (pres[size_t(i)] ? hlen[size_t(i)] : 0);
-      std::vector<uint8_t> bytes(size_t(offs[size_t(nv)]) + 8);
-      if (offs[size_t(nv)]) {
-        DevBuf ddo, dbytes;
-        ddo.alloc(size_t(nv + 1) * 8);
-        dbytes.alloc(size_t(offs[size_t(nv)]) + 8);
-        NBG_HIP(hipMemcpyAsync(ddo.p, offs.data(), size_t(nv + 1) * 8, hipMemcpyHostToDevice, c.stream));
-        k_bytes_gather<<<grid_cap(nv), 256, 0, c.stream>>>(soff.as<int64_t>(), ddo.as<int64_t>(), nv,
-                                                           pc.str_bytes.as<uint8_t>(), dbytes.as<uint8_t>());
-        NBG_HIP(hipMemcpyAsync(bytes.data(), dbytes.p, size_t(offs[size_t(nv)]), hipMemcpyDeviceToHost, c.stream));
-        NBG_HIP(hipStreamSynchronize(c.stream));
-      }
-      h->vertex_host.push_back(std::move(bytes));
-      h->vertex_host_off.push_back(std::move(offs));
-    } else {
-      std::vector<uint8_t> raw(cap * 8);
-      if (pc.type == NBG_T_BOOL) {
-        for (int64_t i = 0; i < nv; i++) raw[size_t(i)] = uint8_t(hv[size_t(i)] != 0);
-      } else {
-        memcpy(raw.data(), hv.data(), size_t(nv) * 8);
-      }
-      h->vertex_host.push_back(std::move(raw));
-      h->vertex_host_off.emplace_back();
-    }
-  }
-}
-
-int32_t get_bound_run(Ctx& c, int32_t et, const int32_t* parts, const int64_t* vids, size_t n, const uint8_t* filter,
-                      size_t flen, const nbg_prop_def* cols, size_t ncols, nbg_rows* out, const int32_t* stats) {
-  PoolScope pool_scope(query_pool(c));
-  if (!c.finalized) throw Error(NBG_E_STATE, "snapshot not finalized");
-  auto h = std::make_unique<HostRows>();
-  auto finish = [&](int64_t nrows) {
-    fill_rows(out, std::move(h), nrows, false);
-    return NBG_OK;
-  };
-  // request-level validation -> every part of the request fails (QueryBaseProcessor.inl:470-477)
-  std::vector<int32_t> req_parts;
-  for (size_t i = 0; i < n; i++)
-    if (std::find(req_parts.begin(), req_parts.end(), parts[i]) == req_parts.end()) req_parts.push_back(parts[i]);
-  auto fail_all = [&](int32_t code) {
-    for (auto p : req_parts) {
-      h->failed_parts.push_back(p);
-      h->failed_codes.push_back(code);
-    }
-    return finish(0);
-  };
-  bool in_bound = et < 0;
-  auto it = c.edges.find(in_bound ? -et : et);
-  if (it == c.edges.end()) return fail_all(NBG_E_EDGE_PROP_NOT_FOUND);
-  EdgeSpace& es = it->second;
-  Csr& csr = in_bound ? es.in : es.out;
-  BoundCols bc{};
-  // SOURCE / DEST tag props: the vertex row of each returned vertex (tagContexts_,
-  // QueryBaseProcessor.inl:40-70; QueryBoundProcessor.cpp:19-31)
-  struct TagReq {
-    const TagSpace* ts;
-    size_t field;
-  };
-  std::vector<TagReq> treq;
-  // stats: the output columns in request order (retIndex): {0, edge column} or {1, tag column}
-  std::vector<std::pair<int, int>> sorder;
-  std::vector<int32_t> tstat;
-  for (size_t i = 0; i < ncols; i++) {
-    if (cols[i].owner != NBG_OWNER_EDGE) {
-      auto tit = c.tags.find(cols[i].tag_id);
-      if (tit == c.tags.end()) return fail_all(NBG_E_TAG_PROP_NOT_FOUND);
-      const std::string tname = cols[i].name ? cols[i].name : "";
-      size_t fi = tit->second.fields.size();
-      for (size_t f = 0; f < tit->second.fields.size(); f++)
-        if (tit->second.fields[f].name == tname) fi = f;
-      if (fi == tit->second.fields.size()) return fail_all(NBG_E_IMPROPER_DATA_TYPE);
-      if (stats) {  // validOperation over the tag prop's type (QueryBaseProcessor.inl:62-64)
-        const int32_t st = stats[i];
-        if (st < 1 || st > 3) throw Error(NBG_E_INVALID_ARG, "stat type must be SUM 1, COUNT 2 or AVG 3");
-        const int32_t t = tit->second.fields[fi].type;
-        if (st != 2 && (t == NBG_T_BOOL || t == NBG_T_STRING)) return fail_all(NBG_E_IMPROPER_DATA_TYPE);
-        sorder.emplace_back(1, int(treq.size()));
-        tstat.push_back(st);
-      }
-      treq.push_back(TagReq{&tit->second, fi});
-      continue;
-    }
-    std::string name = cols[i].name ? cols[i].name : "";
-    BoundCol b{};
-    if (name == "_dst") b.kind = 1;
-    else if (name == "_src") b.kind = 2;
-    else if (name == "_rank") b.kind = 3;
-    else if (name == "_type") b.kind = 4;
-    if (b.kind) {
-      b.type = NBG_T_INT;
-    } else if (!in_bound) {
-      int idx = -1;
-      for (size_t f = 0; f < es.fields.size(); f++)
-        if (es.fields[f].name == name) idx = int(f);
-      if (idx < 0) return fail_all(NBG_E_IMPROPER_DATA_TYPE);
-      b.kind = 0;
-      b.prop = idx;
-      int32_t t = es.fields[size_t(idx)].type;
-      b.type = column_result_type(t);
-    } else {
-      continue;  // "InBound has none props, skip it!"
-    }
-    if (stats) {  // validOperation (QueryBaseProcessor.inl:18-35): SUM / AVG need a numeric column
-      b.stat = stats[i];
-      if (b.stat < 1 || b.stat > 3) throw Error(NBG_E_INVALID_ARG, "stat type must be SUM 1, COUNT 2 or AVG 3");
-      if (b.stat != 2 && (b.type == NBG_T_BOOL || b.type == NBG_T_STRING)) return fail_all(NBG_E_IMPROPER_DATA_TYPE);
-    }
-    if (bc.n >= kMaxBoundCols) throw Error(NBG_E_UNSUPPORTED, "too many return columns");
-    if (stats) sorder.emplace_back(0, bc.n);
-    bc.c[bc.n++] = b;
-  }
-  Program fprog{};
-  FastPred fpk{};
-  if (flen) {
-    std::string msg;
-    int32_t rc = compile_expr(filter, flen, es.fields, false, !in_bound, &fprog, &msg, &c.tag_refs);
-    if (rc == NBG_E_UNSUPPORTED) throw Error(rc, "filter: " + msg);
-    if (rc != NBG_OK) return fail_all(NBG_E_INVALID_FILTER);
-    fpk = classify_pred(fprog, es.fields);
-  }
-  const int pk = fpk.kind;
-  const FastArgs fp = fast_args(csr, fpk);
-  int64_t N = int64_t(n);
-  const int64_t lo = c.owned_lo(), hi = c.owned_hi();
-  // parts not held by this rank -> E_PART_NOT_FOUND (NebulaStore::engine, BaseProcessor.inl:14-27)
-  for (auto p : req_parts)
-    if (p < 0 || p > c.num_parts || owner_of_part(p, c.world) != c.rank) {
-      h->failed_parts.push_back(p);
-      h->failed_codes.push_back(NBG_E_PART_NOT_FOUND);
-    }
-  DevBuf dv, dp, dg, dF, ddeg, doff;
-  dv.alloc(size_t(N + 1) * 8);
-  dp.alloc(size_t(N + 1) * 4);
-  dg.alloc(size_t(N + 1) * 4);
-  dF.alloc(size_t(N + 1) * 4);
-  ddeg.alloc(size_t(N + 1) * 8);
-  doff.alloc(size_t(N + 1) * 8);
-  if (N) {
-    NBG_HIP(hipMemcpyAsync(dv.p, vids, size_t(N) * 8, hipMemcpyHostToDevice, c.stream));
-    NBG_HIP(hipMemcpyAsync(dp.p, parts, size_t(N) * 4, hipMemcpyHostToDevice, c.stream));
-    lookup_gidx(c, dv.as<int64_t>(), dg.as<int32_t>(), N);
-    k_bound_frontier<<<grid_cap(N), 256, 0, c.stream>>>(dp.as<int32_t>(), dg.as<int32_t>(), N, lo, hi,
-                                                      csr.row_part.as<int32_t>(), dF.as<int32_t>());
-  }
-  k_degrees_masked<<<grid_cap(N + 1), 256, 0, c.stream>>>(dF.as<int32_t>(), N, csr.row_ptr.as<int64_t>(), ddeg.as<int64_t>());
-  exclusive_scan_dev<int64_t>(c, ddeg.as<int64_t>(), doff.as<int64_t>(), N + 1);
-  std::vector<int64_t> hoff(size_t(N + 1));
-  NBG_HIP(hipMemcpyAsync(hoff.data(), doff.p, size_t(N + 1) * 8, hipMemcpyDeviceToHost, c.stream));
-  NBG_HIP(hipStreamSynchronize(c.stream));
-  int64_t E = hoff[size_t(N)];
-  c.timing = Timing{};
-  timing_reset(c);
-  if (c.host_stage_used) NBG_HIP(hipStreamSynchronize(c.stream));  // a failed query's copies
-  c.host_stage_used = 0;
-  c.timing.edges_scanned = uint64_t(E);
-  // compress away zero-degree request entries for the expansion (tile owner search needs deg>=1)
-  std::vector<int32_t> hF(static_cast<size_t>(N));
-  if (N) NBG_HIP(hipMemcpy(hF.data(), dF.p, size_t(N) * 4, hipMemcpyDeviceToHost));
-  std::vector<int32_t> cF;
-  std::vector<int64_t> coff, centry;
-  for (int64_t i = 0; i < N; i++)
-    if (hoff[size_t(i + 1)] > hoff[size_t(i)]) {
-      cF.push_back(hF[size_t(i)]);
-      coff.push_back(hoff[size_t(i)]);
-      centry.push_back(i);
-    }
-  coff.push_back(E);
-  int64_t nF = int64_t(cF.size());
-  DevBuf dcF, dcoff, flags, slots, cnt, owner, geb;
-  dcF.alloc(size_t(nF + 1) * 4);
-  dcoff.alloc(size_t(nF + 1) * 8);
-  if (nF) NBG_HIP(hipMemcpyAsync(dcF.p, cF.data(), size_t(nF) * 4, hipMemcpyHostToDevice, c.stream));
-  NBG_HIP(hipMemcpyAsync(dcoff.p, coff.data(), size_t(nF + 1) * 8, hipMemcpyHostToDevice, c.stream));
-  flags.alloc(size_t(E + 1));
-  EvalEnv env = make_env(c, es, csr, in_bound ? -es.type : es.type);
-  env.storage = 1;
-  env.lo = c.owned_lo();
-  env.row_part = csr.row_part.as<int32_t>();
-  DevBuf dprog;
-  dprog.alloc(sizeof(Program));
-  NBG_HIP(hipMemcpyAsync(dprog.p, &fprog, sizeof(Program), hipMemcpyHostToDevice, c.stream));
-  DevBuf cnts;
-  cnts.alloc(64);
-  NBG_HIP(hipMemsetAsync(cnts.p, 0, 64, c.stream));
-  hipEventRecord(c.ev[0], c.stream);
-  int64_t m = 0;
-  if (E > 0) {
-    ExpandArgs a{};
-    a.F = dcF.as<int32_t>();
-    a.nF = nF;
-    a.off = dcoff.as<int64_t>();
-    a.row_ptr = csr.row_ptr.as<int64_t>();
-    a.col = csr.col.as<int32_t>();
-    a.lo = lo;
-    a.flags = flags.as<uint8_t>();
-    a.err = cnts.as<unsigned long long>();
-    a.storage = 1;
-    launch_expand<EXP_FLAGS>(c, a, pk, fp, dprog.as<Program>(), env, E);
-    c.timing.expand_bytes += expand_bytes(nF, E, pk == PK_FAST ? fp.width : 0, EXP_FLAGS);
-    slots.alloc(size_t(E + 1) * 8);
-    cnt.alloc(8);
-    select_dev(c, rocprim::counting_iterator<int64_t>(0), flags.as<uint8_t>(), slots.as<int64_t>(),
-               cnt.as<uint64_t>(), E);
-    uint64_t hm = 0;
-    NBG_HIP(hipMemcpyAsync(&hm, cnt.p, 8, hipMemcpyDeviceToHost, c.stream));
-    NBG_HIP(hipStreamSynchronize(c.stream));
-    m = int64_t(hm);
-  }
-  owner.alloc(size_t(m + 1) * 8);
-  geb.alloc(size_t(m + 1) * 8);
-  if (m) {
-    k_slot_owner<<<grid_cap(m), 256, 0, c.stream>>>(slots.as<int64_t>(), m, dcoff.as<int64_t>(), nF, owner.as<int64_t>());
-    k_slot_ge<<<grid_cap(m), 256, 0, c.stream>>>(slots.as<int64_t>(), owner.as<int64_t>(), m, dcoff.as<int64_t>(),
-                                                 dcF.as<int32_t>(), csr.row_ptr.as<int64_t>(), geb.as<int64_t>());
-    NBG_HIP(hipGetLastError());
-  }
-  // firstLoop (multi-version data under a push-down filter): older versions emitted ahead of a
-  // request entry's rows (QueryBaseProcessor.inl:349-402); the reader only exists for out-bound
-  // rows with a value, so in-bound scans never evaluate the filter
-  DevBuf oldb, ovtab;
-  const PropDev* oprops = nullptr;
-  if (flen && !in_bound && csr.ov_n > 0 && nF > 0) {
-    std::vector<PropDev> tab;
-    for (const PropCol& p : csr.ov_props)
-      tab.push_back(PropDev{p.type, p.width, p.data.p, p.present.as<uint8_t>(), p.str_off.as<int64_t>(),
-                            p.str_bytes.as<uint8_t>()});
-    ovtab.alloc(sizeof(PropDev) * std::max<size_t>(tab.size(), 1));
-    if (!tab.empty()) c.h2d(ovtab.p, tab.data(), sizeof(PropDev) * tab.size());
-    oprops = ovtab.as<PropDev>();
-    EvalEnv oenv = env;
-    oenv.props = oprops;
-    FastArgs ofp{};
-    if (pk == PK_FAST) {
-      const PropCol& oc = csr.ov_props[size_t(fpk.col)];
-      ofp = FastArgs{oc.data.p, oc.present.as<uint8_t>(), 8, fpk.op, fpk.k};
-    }
-    DevBuf xo, xg, cx;
-    xo.alloc(size_t(nF) * 8);
-    xg.alloc(size_t(nF) * 8);
-    cx.alloc(size_t(nF) * 8);
-    if (pk == PK_FAST)
-      k_first_loop<PK_FAST><<<grid_cap(nF), 256, 0, c.stream>>>(dcF.as<int32_t>(), dcoff.as<int64_t>(), nF,
-                                                                csr.row_ptr.as<int64_t>(), flags.as<uint8_t>(),
-                                                                csr.ov_edge.as<int64_t>(), csr.ov_n, dprog.as<Program>(),
-                                                                oenv, ofp, lo, xo.as<int64_t>(), xg.as<int64_t>());
-    else
-      k_first_loop<PK_VM><<<grid_cap(nF), 256, 0, c.stream>>>(dcF.as<int32_t>(), dcoff.as<int64_t>(), nF,
-                                                              csr.row_ptr.as<int64_t>(), flags.as<uint8_t>(),
-                                                              csr.ov_edge.as<int64_t>(), csr.ov_n, dprog.as<Program>(),
-                                                              oenv, ofp, lo, xo.as<int64_t>(), xg.as<int64_t>());
-    NBG_HIP(hipGetLastError());
-    auto has = rocprim::make_transform_iterator(xo.as<int64_t>(), [] __device__(int64_t v) -> int64_t { return v >= 0; });
-    size_t tb = 0;
-    NBG_HIP(rocprim::inclusive_scan(nullptr, tb, has, cx.as<int64_t>(), size_t(nF), rocprim::plus<int64_t>(), c.stream));
-    c.ws_tmp.ensure(tb);
-    NBG_HIP(rocprim::inclusive_scan(c.ws_tmp.p, tb, has, cx.as<int64_t>(), size_t(nF), rocprim::plus<int64_t>(), c.stream));
-    int64_t X = 0;
-    NBG_HIP(hipMemcpyAsync(&X, cx.as<int64_t>() + nF - 1, 8, hipMemcpyDeviceToHost, c.stream));
-    NBG_HIP(hipStreamSynchronize(c.stream));
-    if (X > 0) {
-      DevBuf mge, mold, mown;
-      mge.alloc(size_t(m + X + 1) * 8);
-      mold.alloc(size_t(m + X + 1) * 8);
-      mown.alloc(size_t(m + X + 1) * 8);
-      if (m)
-        k_merge_kept<<<grid_cap(m), 256, 0, c.stream>>>(geb.as<int64_t>(), owner.as<int64_t>(), m, cx.as<int64_t>(),
-                                                        mge.as<int64_t>(), mold.as<int64_t>(), mown.as<int64_t>());
-      k_merge_old<<<grid_cap(nF), 256, 0, c.stream>>>(xo.as<int64_t>(), xg.as<int64_t>(), nF, owner.as<int64_t>(), m,
-                                                      cx.as<int64_t>(), mge.as<int64_t>(), mold.as<int64_t>(),
-                                                      mown.as<int64_t>());
-      NBG_HIP(hipGetLastError());
-      m += X;
-      geb = std::move(mge);
-      owner = std::move(mown);
-      oldb = std::move(mold);
-    }
-  }
-  const int64_t* oldp = oldb.as<int64_t>();
-  if (stats) {
-    // one row: per column SUM (INT) / COUNT (INT) / AVG (DOUBLE), in request order (retIndex)
-    DevBuf acc;
-    acc.alloc(size_t(2 * bc.n + 2) * 8);
-    NBG_HIP(hipMemsetAsync(acc.p, 0, size_t(2 * bc.n + 2) * 8, c.stream));
-    if (m) {
-      for (int i = 0; i < bc.n; i++)
-        k_bound_stats<<<grid_cap(m, 256, 1024), 256, 0, c.stream>>>(geb.as<int64_t>(), oldp, owner.as<int64_t>(), m,
-                                                                    dcF.as<int32_t>(), lo, env, oprops, bc.c[i],
-                                                                    acc.as<unsigned long long>() + 2 * i);
-      NBG_HIP(hipGetLastError());
-    }
-    std::vector<unsigned long long> ha(size_t(2 * bc.n + 2));
-    NBG_HIP(hipMemcpyAsync(ha.data(), acc.p, ha.size() * 8, hipMemcpyDeviceToHost, c.stream));
-    // SOURCE / DEST tag columns (QueryStatsProcessor::processVertex, QueryStatsProcessor.cpp:69-82):
-    // every request entry of an owned part collects the newest version of its vertex row in that
-    // part (collectVertexProps, QueryBaseProcessor.inl:309-333) - visible when the row sits in
-    // the request's part, as for getBound's vertex columns - into the column's sum / count
-    // (StatsCollector, Collector.h:66-94); entries without the row add nothing
-    std::vector<int64_t> tsum(treq.size(), 0), tcnt(treq.size(), 0);
-    std::vector<std::vector<int64_t>> tval(treq.size());
-    std::vector<std::vector<uint8_t>> tstt(treq.size());
-    std::vector<std::vector<int32_t>> tprt(treq.size());
-    DevBuf tv, ts, tp;
-    if (!treq.empty() && N) {
-      tv.alloc(size_t(N) * 8);
-      ts.alloc(size_t(N));
-      tp.alloc(size_t(N) * 4);
-      for (size_t t = 0; t < treq.size(); t++) {
-        const TagSpace& tsp = *treq[t].ts;
-        const PropCol& pc = tsp.cols[treq[t].field];
-        k_tag_fetch<<<grid_cap(N), 256, 0, c.stream>>>(dg.as<int32_t>(), N, pc.data.as<int64_t>(), pc.present.as<uint8_t>(),
-                                                       tsp.part.as<int32_t>(), nullptr, tv.as<int64_t>(), ts.as<uint8_t>(),
-                                                       tp.as<int32_t>(), nullptr, nullptr);
-        NBG_HIP(hipGetLastError());
-        tval[t].resize(size_t(N));
-        tstt[t].resize(size_t(N));
-        tprt[t].resize(size_t(N));
-        NBG_HIP(hipMemcpyAsync(tval[t].data(), tv.p, size_t(N) * 8, hipMemcpyDeviceToHost, c.stream));
-        NBG_HIP(hipMemcpyAsync(tstt[t].data(), ts.p, size_t(N), hipMemcpyDeviceToHost, c.stream));
-        NBG_HIP(hipMemcpyAsync(tprt[t].data(), tp.p, size_t(N) * 4, hipMemcpyDeviceToHost, c.stream));
-        NBG_HIP(hipStreamSynchronize(c.stream));  // the host vectors are reused per column
-      }
-    }
-    hipEventRecord(c.ev[1], c.stream);
-    NBG_HIP(hipStreamSynchronize(c.stream));
-    for (size_t t = 0; t < treq.size() && N; t++) {
-      const int32_t ty = treq[t].ts->cols[treq[t].field].type;
-      for (int64_t i = 0; i < N; i++) {
-        const int32_t rp = parts[i];
-        if (rp < 0 || rp > c.num_parts || owner_of_part(rp, c.world) != c.rank) continue;  // failed part
-        const uint8_t stt = tstt[t][size_t(i)];
-        const bool vis = (stt == 1 && rp == part_of_vid(vids[i], c.num_parts)) || (stt == 2 && rp == tprt[t][size_t(i)]);
-        if (!vis) continue;
-        tcnt[t]++;
-        if (ty == NBG_T_DOUBLE || ty == NBG_T_FLOAT) {
-          if (tstat[t] != 2)
-            throw Error(NBG_E_UNSUPPORTED, "SUM/AVG over a double prop (the reference's int64 sum throws bad_get)");
-        } else if (ty != NBG_T_BOOL && ty != NBG_T_STRING) {
-          tsum[t] = int64_t(uint64_t(tsum[t]) + uint64_t(tval[t][size_t(i)]));
-        }
-      }
-    }
-    float sms = 0;
-    hipEventElapsedTime(&sms, c.ev[0], c.ev[1]);
-    c.timing.total_ms = sms;
-    for (const auto& so : sorder) {
-      if (so.first == 1) {
-        const size_t t = size_t(so.second);
-        const int32_t st = tstat[t];
-        h->types.push_back(st == 3 ? NBG_T_DOUBLE : NBG_T_INT);
-        h->host.emplace_back(8);
-        if (st == 3) {
-          const double avg = double(tsum[t]) / double(int32_t(tcnt[t]));  // count_ is int32 (CommonUtils.h:51)
-          memcpy(h->host.back().data(), &avg, 8);
-        } else {
-          const int64_t v = st == 2 ? int64_t(int32_t(tcnt[t])) : tsum[t];
-          memcpy(h->host.back().data(), &v, 8);
-        }
-        h->str_off.push_back(nullptr);
-        continue;
-      }
-      const int i = so.second;
-      const BoundCol& b = bc.c[i];
-      const int64_t sum = int64_t(ha[size_t(2 * i)]);
-      const int64_t cnt = int64_t(ha[size_t(2 * i + 1)]);
-      if (b.stat != 2 && b.type == NBG_T_DOUBLE && cnt > 0)
-        throw Error(NBG_E_UNSUPPORTED, "SUM/AVG over a double prop (the reference's int64 sum throws bad_get)");
-      h->types.push_back(b.stat == 3 ? NBG_T_DOUBLE : NBG_T_INT);
-      h->host.emplace_back(8);
-      if (b.stat == 3) {
-        const double avg = double(sum) / double(int32_t(cnt));  // count_ is int32 (CommonUtils.h:51)
-        memcpy(h->host.back().data(), &avg, 8);
-      } else {
-        const int64_t v = b.stat == 2 ? int64_t(int32_t(cnt)) : sum;
-        memcpy(h->host.back().data(), &v, 8);
-      }
-      h->str_off.push_back(nullptr);
-    }
-    for (auto& hc : h->host) h->cols.push_back(hc.data());
-    out->edges_scanned = uint64_t(E);
-    return finish(1);
-  }
-  std::vector<DevBuf> dcols(size_t(bc.n));
-  std::vector<DevBuf> slen(size_t(bc.n));
-  for (int i = 0; i < bc.n; i++) {
-    BoundCol& b = bc.c[i];
-    if (b.type == NBG_T_STRING) {
-      slen[size_t(i)].alloc(size_t(m + 1) * 8);
-      b.str_len = slen[size_t(i)].as<int64_t>();
-    } else {
-      dcols[size_t(i)].alloc(size_t(m + 1) * (b.type == NBG_T_BOOL ? 1 : 8));
-      b.out = dcols[size_t(i)].p;
-    }
-  }
-  std::vector<int64_t> howner(static_cast<size_t>(m));
-  if (m) {
-    k_bound_rows<<<grid_cap(m), 256, 0, c.stream>>>(geb.as<int64_t>(), oldp, owner.as<int64_t>(), m,
-                                                  dcF.as<int32_t>(), lo, env, oprops, bc);
-    NBG_HIP(hipGetLastError());
-    NBG_HIP(hipMemcpyAsync(howner.data(), owner.p, size_t(m) * 8, hipMemcpyDeviceToHost, c.stream));
-  }
-  hipEventRecord(c.ev[1], c.stream);
-  NBG_HIP(hipStreamSynchronize(c.stream));
-  float ms = 0;
-  hipEventElapsedTime(&ms, c.ev[0], c.ev[1]);
-  c.timing.total_ms = ms;
-  // assemble: typed columns to host; absent values (INT64_MIN marker / -1 length) stay absent
-  for (int i = 0; i < bc.n; i++) {
-    const BoundCol& b = bc.c[i];
-    h->types.push_back(b.type);
-    if (b.type == NBG_T_STRING) {
-      std::vector<int64_t> lens(static_cast<size_t>(m));
-      if (m) NBG_HIP(hipMemcpy(lens.data(), slen[size_t(i)].p, size_t(m) * 8, hipMemcpyDeviceToHost));
-      std::vector<int64_t> offs(size_t(m) + 1, 0);
-      for (int64_t r = 0; r < m; r++) offs[size_t(r + 1)] = offs[size_t(r)] + std::max<int64_t>(lens[size_t(r)], 0);
-      DevBuf doffs, dbytes;
-      doffs.alloc(size_t(m + 1) * 8);
-      dbytes.alloc(size_t(offs[size_t(m)]) + 8);
-      NBG_HIP(hipMemcpy(doffs.p, offs.data(), size_t(m + 1) * 8, hipMemcpyHostToDevice));
-      const PropCol& pc = csr.props[size_t(b.prop)];
-      if (m)
-        k_str_gather<<<grid_cap(m), 256, 0, c.stream>>>(
-            geb.as<int64_t>(), oldp, m, pc.str_off.as<int64_t>(), pc.str_bytes.as<uint8_t>(),
-            oldp ? csr.ov_props[size_t(b.prop)].str_off.as<int64_t>() : nullptr,
-            oldp ? csr.ov_props[size_t(b.prop)].str_bytes.as<uint8_t>() : nullptr, doffs.as<int64_t>(),
-            dbytes.as<uint8_t>());
-      NBG_HIP(hipStreamSynchronize(c.stream));
-      h->host.emplace_back(size_t(offs[size_t(m)]) + 8);
-      if (offs[size_t(m)]) NBG_HIP(hipMemcpy(h->host.back().data(), dbytes.p, size_t(offs[size_t(m)]), hipMemcpyDeviceToHost));
-      h->host_off.push_back(offs);
-      h->cols.push_back(h->host.back().data());
-      h->str_off.push_back(h->host_off.back().data());
-    } else {
-      size_t w = b.type == NBG_T_BOOL ? 1 : 8;
-      h->host.emplace_back(size_t(m) * w + 8);
-      if (m) NBG_HIP(hipMemcpy(h->host.back().data(), dcols[size_t(i)].p, size_t(m) * w, hipMemcpyDeviceToHost));
-      h->cols.push_back(h->host.back().data());
-      h->str_off.push_back(nullptr);
-    }
-  }
-  // vertices with >= 1 row, in request order (QueryBoundProcessor.cpp:61-67)
-  h->row_vertex.resize(size_t(m));
-  int64_t last = -1;
-  for (int64_t r = 0; r < m; r++) {
-    int64_t k = howner[size_t(r)];
-    int64_t entry = centry[size_t(k)];
-    h->row_vertex[size_t(r)] = vids[entry];
-    if (k != last) {
-      h->vertex_ids.push_back(vids[entry]);
-      h->vertex_row_offsets.push_back(r);
-      last = k;
-    }
-  }
-  h->vertex_row_offsets.push_back(m);
-  if (!treq.empty()) {
-    // request part of each returned vertex (its first request entry)
-    std::vector<int32_t> vparts;
-    last = -1;
-    for (int64_t r = 0; r < m; r++) {
-      int64_t k = howner[size_t(r)];
-      if (k != last) vparts.push_back(parts[centry[size_t(k)]]);
-      last = k;
-    }
-    fetch_vertex_tags(c, h.get(), vparts, [&](size_t t) { return std::make_pair(treq[t].ts, treq[t].field); },
-                      treq.size());
-  }
-  fill_rows(out, std::move(h), m, false);
-  out->edges_scanned = uint64_t(E);
-  return NBG_OK;
 }
 
 void free_rows_impl(void* impl) { delete static_cast<HostRows*>(impl); }
