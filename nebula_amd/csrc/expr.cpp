@@ -377,10 +377,8 @@ FastPred classify_pred(const Program& p, const std::vector<Field>& fields) {
       return t == NBG_T_INT || t == NBG_T_VID || t == NBG_T_TIMESTAMP;
     };
     auto is_int_const = [&](const Ins& i) { return i.op == P_CONST && p.ctype[i.arg] == VT_INT; };
-    static const int swap_op[6] = {3 /*LT->GT*/, 2 /*LE->GE*/, 1 /*GT->LT*/, 0 /*GE->LE*/, 4, 5};
     // LT=0 LE=1 GT=2 GE=3 EQ=4 NE=5; a<b == b>a
     static const int mirror[6] = {2, 3, 0, 1, 4, 5};
-    (void)swap_op;
     if (is_int_prop(a) && is_int_const(b)) {
       f.kind = 1;
       f.col = a.arg;

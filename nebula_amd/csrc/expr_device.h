@@ -6,6 +6,7 @@
 
 #include "../../include/nebula_amd.h"
 #include "program.h"
+#include "qpred.h"
 
 namespace nbg {
 
@@ -303,16 +304,6 @@ struct FastArgs {
   int32_t op;
   int64_t k;
 };
-
-__host__ __device__ inline bool fast_cmp(int op, int64_t a, int64_t k) {
-  switch (op) {
-    case 0: return a < k;
-    case 1: return a <= k;
-    case 2: return a > k;
-    case 3: return a >= k;
-    case 4: return a == k;
-    default: return a != k;
-  }
-}
+// the compare itself: fast_cmp (qpred.h)
 
 }  // namespace nbg

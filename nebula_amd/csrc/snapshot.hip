@@ -23,6 +23,7 @@
 
 #include "device_common.h"
 #include "engine.h"
+#include "qpred.h"
 #include "query_common.h"
 
 namespace nbg {
@@ -1497,12 +1498,6 @@ __global__ void k_minmax_w(const void* data, int w, int64_t m, long long* mm) {
     atomicMax(mm + 1, hi);
   }
 }
-// the quantised bucket of v: floor((v - min) * 2^bits / range) (range 0 = 2^64)
-__host__ __device__ inline uint32_t q_bucket(int64_t v, int64_t vmin, uint64_t range, int bits) {
-  const unsigned __int128 d = (unsigned __int128)(uint64_t(v) - uint64_t(vmin)) << bits;
-  const unsigned __int128 r = range ? (unsigned __int128)range : ((unsigned __int128)1 << 64);
-  return uint32_t(d / r);
-}
 // packed transposed column: (bucket << gbits) | src gidx
 __global__ void k_pack_col(const int32_t* col, const void* data, int w, int64_t m, int64_t vmin, uint64_t range,
                            int gbits, int qbits, int32_t* out) {
@@ -1730,8 +1725,12 @@ static void build_transpose(Ctx& c, EdgeSpace& es) {
   es.q_gbits = es.q_bits = 0;
   es.tcol_q.release();
   if (R > 0) {
-    // 2^gb > n_global: an empty slot (-1) decodes to a gidx past every vertex, whose bitmap
-    // probe is out of bounds (k_bu_lean relies on it)
+    // 2^gb > n_global: an empty slot (-1) decodes to gidx 2^gb - 1, past every vertex.  Its bitmap
+    // probe is out of bounds (and answers 0) unless n_global > 2^gb - 32; then it is in bounds
+    // (n_global = 2^gb - 1: bit 31 of the last word) and reads a bit no vertex owns, which no
+    // frontier bitmap ever has set: the start bitmap and the top-down marks set bits of real gidx
+    // only, and a bottom-up hop finds a row only through a set bit, so the pad rows of the last
+    // tile (all slots empty) stay unfound (k_bu_lean, k_bu_fin and k_bu_rest_lean rely on it)
     int gb = 1;
     while ((int64_t(1) << gb) <= c.n_global) gb++;
     const int qb = std::min(8, 31 - gb);

@@ -32,6 +32,7 @@
 #include "engine.h"
 #include "expr_device.h"
 #include "program.h"
+#include "qpred.h"
 #include "query_common.h"
 #include "rows.h"
 
@@ -44,18 +45,7 @@ constexpr int kTile = kThreads * kItems;
 // ------------------------------------------------------------------------------------------
 // expansion
 // ------------------------------------------------------------------------------------------
-// Quantised predicate on packed bottom-up words (EdgeSpace::q_*): the low gbits bits are the
-// source gidx, the bits above the bucket of the predicate column's value.  The compare decides
-// every bucket below ulo (`below`: 1 pass, 0 fail) and above uhi (`above`); buckets in
-// [ulo, uhi] hold the constant and need the exact value (-1).  Host-built per query
-// (make_qargs); all scalars, so the test is two compares, no table loads.  Unpacked words:
-// gmask all ones, ulo 0, uhi INT_MAX (every word undecided).
-struct QArgs {
-  uint32_t gmask = 0xffffffffu;
-  int32_t gbits = 0;
-  int32_t ulo = 0, uhi = INT32_MAX;
-  int32_t below = -1, above = -1;
-};
+// Quantised predicate on packed bottom-up words: QArgs / q_test (qpred.h).
 // The kernels' copy of QArgs in scalar registers.  Read through the by-value kernel argument,
 // q_test's select between `below` and `above` compiled to a per-lane select of two kernarg
 // addresses and a vector load, i.e. one dependent load and a vmcnt(0) wait per slot word.
@@ -70,14 +60,6 @@ __device__ inline QArgs q_sgpr(const QArgs& a) {
   return r;
 }
 __device__ inline int32_t q_gidx(int32_t s, const QArgs& q) { return s & int32_t(q.gmask); }
-// 1 pass, 0 fail, -1 undecided (load the value)
-__device__ inline int q_test(int32_t s, const QArgs& q) {
-  const int32_t b = int32_t(uint32_t(s) >> q.gbits);
-  int r = -1;
-  r = b > q.uhi ? q.above : r;
-  r = b < q.ulo ? q.below : r;
-  return r;
-}
 
 template <int MODE, int PK>
 __global__ __launch_bounds__(kThreads) void k_expand(ExpandArgs a, FastArgs fp, const Program* __restrict__ prog,
@@ -907,19 +889,19 @@ __global__ __launch_bounds__(1024, 8) void k_bu_lean(const uint2* __restrict__ l
 // waves busy issuing, 225 VALU per 128-row tile, the HBM stream at 4 TB/s).  FinArgs, host-built
 // per query (fin_args): a word is a candidate iff (w - clo) <= cr, it passes iff
 // ((w - plo) <= pr) != pinv (the bucket field sits above the gidx bits, so bucket ranges are
-// word ranges; the -1 pad word is either no candidate or probes past the bitmap).  A candidate's
+// word ranges; the -1 pad word is a candidate of every range that reaches the top field: its
+// probe, gidx 2^gbits - 1, is past the bitmap or, when n_global > 2^gbits - 32, reads a bit of
+// the last word that no vertex owns and no frontier sets, see build_transpose).  A candidate's
 // probe byte offset is (w >> 3) & bmask, a non-candidate's kNoProbe; the global probe reads
 // through a resource based cw words into the bitmap (hub words wrap out of bounds: the hardware
 // returns 0), the LDS probe reads min(offset, 4 cw) (the zero word past the hub copy).
-struct FinArgs {
-  uint32_t clo = 0, cr = 0xffffffffu, plo = 0, pr = 0xffffffffu;
-  uint32_t pinv = 0, bmask = 0xfffffffcu;
-};
 constexpr uint32_t kNoProbe = 0x0ffffff0u;
 // CLS 1: the candidates are every word from clo up and the passing ones every word from plo up
 // (pinv 0): the "greater than" compares, the benchmark's.  A non-candidate's offset then comes
 // from the sign of w - clo (all ones: past the bitmap and clamped to the zero word) instead of
-// a compare and a select, and the pass test is one compare.
+// a compare and a select, and the pass test is one compare.  The sign test is stricter than the
+// range test on the -1 pad word alone: while clo < 2^31 it sends the pad no probe at all, where
+// the generic form probes the unowned bit (the same answer: that bit is never set).
 // NT: non-temporal slab loads (the slab is read once per hop; the bitmap the probes hit stays
 // in L2): 158 -> 148 us at C3.  Measured without gain (r04f/r04g): the next tile's slab loads
 // issued behind the current tile's probes, an interleaved 16-byte slab (one load per row), two
@@ -992,9 +974,9 @@ __global__ __launch_bounds__(1024, 8) void k_bu_fin(const uint2* __restrict__ lo
       for (int k = 0; k < NS; k++) {
         const uint32_t w = sw[h][k];
         if (CLS == 1)
-          ob[h][k] = ((w >> 3) & bmask) | uint32_t(int32_t(w - clo) >> 31);
+          ob[h][k] = ((w >> 3) & bmask) | fin_skip_cls1(w, clo);
         else
-          ob[h][k] = w - clo <= cr ? (w >> 3) & bmask : kNoProbe;
+          ob[h][k] = fin_candidate(w, clo, cr) ? (w >> 3) & bmask : kNoProbe;
       }
     uint32_t lw[2][4], gw[2][4];
 #pragma unroll
@@ -1009,7 +991,7 @@ __global__ __launch_bounds__(1024, 8) void k_bu_fin(const uint2* __restrict__ lo
 #pragma unroll
       for (int k = 0; k < NS; k++) {
         const uint32_t w = sw[h][k];
-        const bool pass = CLS == 1 ? w >= plo : (w - plo <= pr) != pinv;
+        const bool pass = CLS == 1 ? w >= plo : (w - plo <= pr) != pinv;  // qpred.h fin_pass_cls1 / fin_pass
         hubf[h] = hubf[h] || (__builtin_amdgcn_ubfe(lw[h][k], w, 1u) != 0u && pass);
       }
     // a probe instruction only when some lane of the wave has an L2 candidate in that slot
@@ -1030,7 +1012,7 @@ __global__ __launch_bounds__(1024, 8) void k_bu_fin(const uint2* __restrict__ lo
       for (int k = 0; k < NS; k++) {
         const uint32_t w = sw[h][k];
         const bool hit = __builtin_amdgcn_ubfe(lw[h][k] | gw[h][k], w, 1u) != 0u;
-        const bool pass = CLS == 1 ? w >= plo : (w - plo <= pr) != pinv;
+        const bool pass = CLS == 1 ? w >= plo : (w - plo <= pr) != pinv;  // qpred.h fin_pass_cls1 / fin_pass
         fh = fh || (hit && pass);
         ah = ah || hit;
       }
@@ -2485,62 +2467,15 @@ void launch_expand(Ctx& c, ExpandArgs a, int pk, const FastArgs& fp, const Progr
   c.timing.expand_launches++;
 }
 
-// values min + [ceil(b * range / 2^bits), ceil((b + 1) * range / 2^bits) - 1]; it passes (fails)
-// when every value in it passes (fails) the compare, else the kernels read the exact value.
+// QArgs of a hop on es: unpacked words, packed words whose every value is read (no typed
+// compare, or one on another column than the packed one), or the bucket decisions (qpred.h).
 QArgs make_qargs(const EdgeSpace& es, int pk, int fcol, const FastArgs& fp) {
   QArgs q;
   if (es.q_field < 0) return q;
   q.gmask = (1u << es.q_gbits) - 1u;
   q.gbits = es.q_gbits;
   if (pk != PK_FAST || fcol != es.q_field) return q;  // packed words, every value read
-  using u128 = unsigned __int128;
-  const u128 R = es.q_range ? u128(es.q_range) : (u128(1) << 64);
-  const int bits = es.q_bits, nb = 1 << bits;
-  auto edge = [&](uint64_t b) -> u128 { return ((u128(b) * R) + ((u128(1) << bits) - 1)) >> bits; };  // ceil
-  // per bucket: 1 pass, 0 fail, -1 undecided, 2 empty (no value lands there: either answer)
-  std::vector<int> dec(size_t(nb), 2);
-  for (int b = 0; b < nb; b++) {
-    const u128 o0 = edge(uint64_t(b)), o1 = edge(uint64_t(b) + 1);
-    if (o0 >= o1) continue;
-    const int64_t lo = int64_t(uint64_t(es.q_min) + uint64_t(o0));
-    const int64_t hi = int64_t(uint64_t(es.q_min) + uint64_t(o1 - 1));
-    const int64_t k = fp.k;
-    bool pass, fail;
-    if (fp.op == 4) {  // ==
-      pass = lo == k && hi == k;
-      fail = k < lo || k > hi;
-    } else if (fp.op == 5) {  // !=
-      pass = k < lo || k > hi;
-      fail = lo == k && hi == k;
-    } else {  // monotone compares: both ends decide the bucket
-      const bool x = fast_cmp(fp.op, lo, k), z = fast_cmp(fp.op, hi, k);
-      pass = x && z;
-      fail = !x && !z;
-    }
-    dec[size_t(b)] = pass ? 1 : fail ? 0 : -1;
-  }
-  // below: the first non-empty bucket's answer, up to the first bucket answering otherwise;
-  // above: the last one's, down to the last bucket answering otherwise; between: undecided
-  int first = 2, last = 2;
-  for (int b = 0; b < nb && first == 2; b++) first = dec[size_t(b)];
-  for (int b = nb - 1; b >= 0 && last == 2; b--) last = dec[size_t(b)];
-  if (first == 2) return q;  // no values at all
-  int ulo = nb, uhi = nb - 1;
-  for (int b = 0; b < nb; b++)
-    if (dec[size_t(b)] != 2 && dec[size_t(b)] != first) {
-      ulo = b;
-      break;
-    }
-  for (int b = nb - 1; b >= 0; b--)
-    if (dec[size_t(b)] != 2 && dec[size_t(b)] != last) {
-      uhi = b;
-      break;
-    }
-  q.ulo = ulo;
-  q.uhi = ulo == nb ? nb - 1 : uhi;
-  q.below = first;
-  q.above = ulo == nb ? first : last;
-  return q;
+  return make_qargs_core(es.q_min, es.q_range, es.q_bits, es.q_gbits, fp.op, fp.k);
 }
 
 // DISTINCT _dst output: the vids of a bitmap's set rows (8 word pairs per lane and step; r05
@@ -2551,49 +2486,6 @@ static void launch_bits_vids(Ctx& c, const uint32_t* bits, int64_t rows, int64_t
   // L2 as dirty lines): 0.4048 -> 0.4001 ms a C3 query, 4 A/B pairs (+ 3: 0.403 -> 0.397)
   const int grid = grid_cap((rows + 31) / 32, 1024, 4096);
   k_bits_compact<1, 8, 1><<<grid, 1024, 0, c.stream>>>(bits, rows, lo, c.vid_of.as<int64_t>(), out, n_out, gate);
-}
-
-// k_bu_fin's word ranges from a query's bucket decisions (q_test: buckets below ulo answer
-// `below`, above uhi `above`, the rest are undecided).  The field above the gidx bits is the
-// bucket; every decision region is a contiguous field range, so each set is one word range.
-FinArgs fin_args(const QArgs& q) {
-  FinArgs f;
-  const int gb = q.gbits;
-  f.bmask = (q.gmask >> 3) & ~3u;
-  if (gb <= 0) {  // unpacked words: no buckets (every word undecided, or no predicate at all)
-    f.clo = 0, f.cr = 0xffffffffu;
-    const bool all_pass = q.below == 1 && q.above == 1;
-    f.plo = 0, f.pr = 0xffffffffu, f.pinv = all_pass ? 0u : 1u;
-    return f;
-  }
-  const int64_t B = (int64_t(1) << (32 - gb)) - 1;  // largest field value (the -1 pad's)
-  const int64_t lo_end = std::min<int64_t>(std::max<int64_t>(q.ulo, 0), B + 1);  // [0, lo_end): below
-  const int64_t u_end = std::min<int64_t>(std::max<int64_t>(q.uhi, lo_end - 1), B);  // [lo_end, u_end]: undecided
-  auto word_lo = [&](int64_t a) { return uint32_t(uint64_t(a) << gb); };
-  auto word_hi = [&](int64_t b) { return uint32_t(((uint64_t(b) + 1) << gb) - 1); };
-  auto set_range = [&](int64_t a, int64_t b, uint32_t& lo, uint32_t& r) {  // field range [a, b], a <= b
-    lo = word_lo(a);
-    r = word_hi(b) - lo;
-  };
-  const bool c0 = q.below != 0, c2 = q.above != 0;  // below / above regions are candidates
-  if (c0 && c2) set_range(0, B, f.clo, f.cr);
-  else if (c0) set_range(0, u_end, f.clo, f.cr);
-  else if (c2) set_range(lo_end, B, f.clo, f.cr);
-  else if (lo_end <= u_end) set_range(lo_end, u_end, f.clo, f.cr);
-  else f.clo = 0xffffffffu, f.cr = 0;  // no candidate but the pad word (whose probe is out of bounds)
-  const bool p0 = q.below == 1 && lo_end > 0, p2 = q.above == 1 && u_end < B;
-  f.pinv = 0;
-  if (p0 && p2) {
-    if (lo_end <= u_end) set_range(lo_end, u_end, f.plo, f.pr), f.pinv = 1;  // all but the undecided
-    else f.plo = 0, f.pr = 0xffffffffu;
-  } else if (p0) {
-    set_range(0, lo_end - 1, f.plo, f.pr);
-  } else if (p2) {
-    set_range(u_end + 1, B, f.plo, f.pr);
-  } else {
-    f.plo = 0, f.pr = 0xffffffffu, f.pinv = 1;  // nothing passes
-  }
-  return f;
 }
 
 // bottom-up hop: the first pass (k_bu_lean) over the quad slab and the pending rows' rests in
@@ -2693,8 +2585,7 @@ BuLaunch launch_bu_lean(Ctx& c, EdgeSpace& es, const uint32_t* fb, uint32_t* nbi
   if (fin) {
     const FinArgs fa = fin_args(q);
     // CLS 1 ("greater than"): candidates and passing words are each one upper range
-    const bool cls1 = fa.pinv == 0 && fa.cr == ~fa.clo && fa.pr == ~fa.plo && fa.clo <= 0x80000000u &&
-                      fa.plo <= 0x80000000u && c.opt("bu_fin_cls", 1) != 0;
+    const bool cls1 = fin_cls1_ok(fa) && c.opt("bu_fin_cls", 1) != 0;
     const size_t fshm = size_t((cw + 2) & ~1) * 4 + size_t(kSlots) * 16 * 8;
     const uint32_t rest = fb_bytes > uint32_t(cw) * 4u ? fb_bytes - uint32_t(cw) * 4u : 0u;
     const int nt = int(c.opt("bu_fin_nt", 1) != 0);
@@ -2984,6 +2875,8 @@ struct GoQuery {
   // clean_shards zeroes them again before any later dense use of the same words.
   int ks = 1;
   bool shards_dirty = false;
+  // a host-chosen bottom-up hop's HopWord block lies over [kCntList, kHopWords) (kCntWhereErr too)
+  bool hop_words_stale = false;
 
   // ---- frontier state: a list of local rows (top-down) and/or a bitmap (bottom-up) ----
   int32_t* F = nullptr;
@@ -3619,6 +3512,7 @@ struct GoQuery {
     const BuLaunch L = timed_bu(c.timing.n_hops, [&] {
       return launch_bu_lean(c, es, fb, bitsB, es.odeg.as<uint32_t>(), PK_NONE, no_fp, -1, K.d, step > 1);
     });
+    hop_words_stale = true;
     if (multi) dev_allsum(c, K.d, {kHopFound, kHopDegSum}, K.d + kCntGlobal);
     fetch_counters(c, K.d, multi ? kCntGlobal + 2 : kHopWords, K.h);
     record_bu_hop(K.h, L);
@@ -3752,6 +3646,10 @@ struct GoQuery {
       record_bu_hop(K.h + kCntFinalHop, L, true, nrows);
     } else {
       vids.alloc(size_t(c.n_global + 64) * 8);
+      // a host-chosen bottom-up hop before this one left its HopWord block in [0, kHopWords):
+      // kHopEntries is this word (else it is still zero: nothing else writes it before here)
+      if (hop_words_stale) NBG_HIP(hipMemsetAsync(K.d + kCntWhereErr, 0, 8, c.stream));
+      hop_words_stale = false;
       expand_marks(true);
       DevBuf lst;
       lst.alloc(size_t(n_own + 64) * 4);
