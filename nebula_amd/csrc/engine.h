@@ -381,6 +381,11 @@ struct EdgeSpace {
   // two halves (slots 0-1 -> pair_col[0], slots 2-3 -> pair_col[1], 2 x int32 per row, -1 past
   // the row's end, padded to whole 128-row tiles)
   DevBuf pair_col[2];
+  // uint32 words, one bit per 128-row slab tile: set iff some owned row of the tile has a third
+  // entry; in a clear tile pair_col[1] is all pad and the final first pass does not read it.
+  // Built with the slab from the same row_ptr (exact whatever the numbering); one word of
+  // padding past the last tile's word.
+  DevBuf tile_wide;
   // quantised predicate packing (bottom-up hops): the words of pair_col and tcol_q carry the
   // source gidx in their low q_gbits bits and, above it, q_bits bits of the bucket of transposed
   // prop q_field's value: bucket(v) = (v - q_min) * 2^q_bits / q_range (monotone), so a

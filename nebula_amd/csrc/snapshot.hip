@@ -507,6 +507,7 @@ static void reset_transpose_derived(EdgeSpace& es) {
   es.q_field = -1;
   es.q_gbits = es.q_bits = 0;
   for (int h = 0; h < 2; h++) es.pair_col[h].release();
+  es.tile_wide.release();
   es.odeg.release();
   es.odeg8.release();
   es.max_odeg = -1;
@@ -1519,6 +1520,19 @@ __global__ void k_build_pair(const int64_t* trp, const T* src, int64_t n, T* lo,
   }
 }
 
+// EdgeSpace::tile_wide: bit t set iff a row of 128-row tile t has at least 3 entries (slots 2-3 of
+// the tile's other rows are all pad).  A wave covers 64 consecutive rows per step: one atomic
+// per half tile with such a row.  `wide` is zeroed by the caller.
+__global__ void k_tile_wide(const int64_t* trp, int64_t n, uint32_t* wide) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t b = blockIdx.x * int64_t(blockDim.x) + threadIdx.x - lane; b < n; b += int64_t(gridDim.x) * blockDim.x) {
+    const int64_t d = b + lane;
+    const bool w = d < n && trp[d + 1] - trp[d] >= 3;
+    const int64_t t = b >> 7;
+    if (__ballot(w) != 0ull && lane == 0) atomicOr(wide + (t >> 5), 1u << (uint32_t(t) & 31u));
+  }
+}
+
 // rest records (EdgeSpace::brec): row d's start and clamped in-degree, then its first
 // kRecEntries entries of src, as one 64-byte line (four 16-byte stores)
 __global__ void k_build_rec(const int64_t* trp, const int32_t* src, int64_t n, uint4* rec) {
@@ -1721,6 +1735,7 @@ static void build_transpose(Ctx& c, EdgeSpace& es) {
   // the quad slab of the bottom-up first pass (k_bu_lean), packed with the quantised bucket of
   // the first INT-like transposed prop when the gidx leaves >= 3 spare bits below bit 31
   for (int h = 0; h < 2; h++) es.pair_col[h].release();
+  es.tile_wide.release();
   es.q_field = -1;
   es.q_gbits = es.q_bits = 0;
   es.tcol_q.release();
@@ -1771,6 +1786,14 @@ static void build_transpose(Ctx& c, EdgeSpace& es) {
       k_build_pair<int32_t><<<grid_for(n_own), 256, 0, c.stream>>>(t.row_ptr.as<int64_t>(), src_col, n_own,
                                                                    es.pair_col[0].as<int32_t>(),
                                                                    es.pair_col[1].as<int32_t>(), -1);
+    // one bit per tile: some row of it has a third entry (from the row_ptr the slab was cut from,
+    // so exact whatever the numbering); a word of padding past the last tile's, k_bu_fin reads
+    // its next tile's word ahead
+    const int64_t nt = n_pad / 128;
+    es.tile_wide.alloc(size_t(nt / 32 + 2) * 4);
+    NBG_HIP(hipMemsetAsync(es.tile_wide.p, 0, size_t(nt / 32 + 2) * 4, c.stream));
+    if (n_own)
+      k_tile_wide<<<grid_for(n_own), 256, 0, c.stream>>>(t.row_ptr.as<int64_t>(), n_own, es.tile_wide.as<uint32_t>());
   }
   {
     // exact row bounds of the bottom-up hops: past the last row with an in-edge nothing can be
@@ -1825,7 +1848,11 @@ __global__ void k_count_deg(const int64_t* src, int64_t n, const int64_t* keys, 
 }
 // Vertex numbering key (sorted ascending, stable over vids ascending): the degree class above
 // the complemented out-degree.  Classes: 0 both in- and out-edges, 1 in-edges only, 2 out-edges
-// only, 3 none (ideg null: every vertex class 0, plain descending out-degree).  A bottom-up hop
+// only, 3 none (ideg null: every vertex class 0, plain descending out-degree); below the
+// out-degree, two bits of descending min(in-degree, 3), so the rows with at most two in-edges
+// -- nearly all of them in the long equal-out-degree runs, class 1 whole among them -- gather
+// at the end of their run and fill whole tiles whose slots 2-3 are pad (tile_wide clear; the
+// hubs, of distinct out-degrees, keep their places).  A bottom-up hop
 // then works on a prefix of the rows: a non-final hop on class 0 (a row needs an in-edge to be
 // found and an out-edge to matter), the final hop on classes 0-1 (snapshot: bu_both_tiles,
 // bu_in_tiles, exact bounds whatever the order).  idx (streamed RMAT build): counts are indexed
@@ -1835,12 +1862,13 @@ __global__ void k_class_key(const unsigned int* odeg, const unsigned int* ideg, 
   for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) {
     const int64_t u = idx ? int64_t(idx[i]) : i;
     const uint32_t od = odeg[u];
-    uint64_t cls = 0;
     if (ideg) {
       const uint32_t id = ideg[u];
-      cls = id ? (od ? 0 : 1) : (od ? 2 : 3);
+      const uint64_t cls = id ? (od ? 0 : 1) : (od ? 2 : 3);
+      key[i] = (cls << 34) | (uint64_t(~od) << 2) | uint64_t(3u - min(id, 3u));
+    } else {
+      key[i] = uint64_t(~od);
     }
-    key[i] = (cls << 32) | uint64_t(~od);
   }
 }
 
@@ -1903,7 +1931,7 @@ static void order_by_degree(Ctx& c, DevBuf& owned, int64_t n_owned) {
   k_class_key<<<grid_for(n_owned), 256, 0, c.stream>>>(deg.as<unsigned int>(), classes ? ideg.as<unsigned int>() : nullptr,
                                                        nullptr, n_owned, key.as<uint64_t>());
   radix_pairs<uint64_t, uint64_t>(c, key.as<uint64_t>(), keyS.as<uint64_t>(), owned.as<uint64_t>(),
-                                 sorted.as<uint64_t>(), n_owned, classes ? 34 : 32);
+                                 sorted.as<uint64_t>(), n_owned, classes ? 36 : 32);
   NBG_HIP(hipMemcpyAsync(owned.p, sorted.p, size_t(n_owned) * 8, hipMemcpyDeviceToDevice, c.stream));
   NBG_HIP(hipStreamSynchronize(c.stream));
   NBG_HIP(hipGetLastError());
@@ -2635,7 +2663,7 @@ static void finalize_rmat_stream(Ctx& c, EdgeSpace& es) {
     k_class_key<<<grid_for(n), 256, 0, c.stream>>>(odeg_u.as<unsigned int>(), classes ? ideg_u.as<unsigned int>() : nullptr,
                                                    idxB.as<uint32_t>(), n, d1.as<uint64_t>());
     radix_pairs<uint64_t, uint32_t>(c, d1.as<uint64_t>(), d2.as<uint64_t>(), idxB.as<uint32_t>(), idxA.as<uint32_t>(),
-                                    n, classes ? 34 : 32);
+                                    n, classes ? 36 : 32);
     order = idxA.as<uint32_t>();
   }
   // 3. vertex map (one rank: base = [0, n padded to 64])

@@ -26,6 +26,7 @@
 #include <cmath>
 #include <unordered_map>
 #include <thread>
+#include <type_traits>
 #include <initializer_list>
 
 #include "device_common.h"
@@ -914,6 +915,10 @@ constexpr uint32_t kNoProbe = 0x0ffffff0u;
 // LDS scratch.  Round 5, removed in round 6: the 3-slot slab (12 B a row, slot 2 flagging a fourth
 // entry in bit 31): this pass 106.9 -> 90.5 us but the rest pass 43 -> 74 us, the query 0.413 ->
 // 0.425 ms (r10e).
+// Two-slot tiles (wide: EdgeSpace::tile_wide, nullptr = every tile has four slots): a tile whose
+// bit is clear has no row with a third entry, so its slots 2-3 are pad; the wave loads `lo`
+// only and runs the pipeline for slots 0-1 (a wave-uniform run-time branch: the kernel keeps
+// its two template parameters, profiles and tests go by its name).  DESIGN.md section 6.
 template <int CLS, int NT>
 __global__ __launch_bounds__(1024, 8) void k_bu_fin(const uint2* __restrict__ lo, const uint2* __restrict__ hi,
                                                     int64_t ntiles, int64_t work_tiles,
@@ -922,7 +927,7 @@ __global__ __launch_bounds__(1024, 8) void k_bu_fin(const uint2* __restrict__ lo
                                                     unsigned long long* __restrict__ pbits, FinArgs fa_arg,
                                                     unsigned long long* __restrict__ partials, int cw,
                                                     uint32_t fb_rest, unsigned long long* gate, GateIn gi,
-                                                    int atomic_sums) {
+                                                    int atomic_sums, const uint32_t* __restrict__ wide) {
   if (!gate_open(gi, gate)) return;  // a speculative hop that the direction choice did not take
   // dynamic LDS only, so the hub copy starts at address 0 and a probe's LDS address is its
   // clamped byte offset as it is: [0, cw) the bitmap's hub words, [cw] a zero word, then the
@@ -943,7 +948,9 @@ __global__ __launch_bounds__(1024, 8) void k_bu_fin(const uint2* __restrict__ lo
   // probe's address is its clamped byte offset (a pointer form cost an add per probe)
   typedef const __attribute__((address_space(3))) uint32_t* lds_u32p;
   const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
+  // (in a scalar register: the tile index picks the tile's path and its tile_wide word)
+  const int64_t wave =
+      int64_t(__builtin_amdgcn_readfirstlane(uint32_t((int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6)));
   const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
   unsigned long long nfound = 0, npend = 0, nwords = 0;  // wave-uniform
   auto ld8 = [&](const uint2* p) -> uint2 {
@@ -951,23 +958,24 @@ __global__ __launch_bounds__(1024, 8) void k_bu_fin(const uint2* __restrict__ lo
     const uint64_t x = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(p));
     return make_uint2(uint32_t(x), uint32_t(x >> 32));
   };
-  constexpr int NS = 4;  // slots per row
-  auto load = [&](int64_t t, uint32_t (&sw)[2][4]) {
+  const uint32_t rest_b = __builtin_amdgcn_readfirstlane(fb_rest);
+  // one tile, NS slots per row: 4, or 2 for a tile whose rows all have at most two entries
+  // (its slots 2-3 are pad: no candidate, no hit, no fifth entry -- not loaded, not probed)
+  auto tile = [&](int64_t t, auto ns_c) {
+    constexpr int NS = decltype(ns_c)::value;
+    uint32_t sw[2][NS];
     const int64_t r = t * 128 + lane;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       const uint2 a = ld8(lo + r + 64 * h);
       sw[h][0] = a.x, sw[h][1] = a.y;
-      const uint2 b = ld8(hi + r + 64 * h);
-      sw[h][2] = b.x, sw[h][3] = b.y;
+      if (NS == 4) {
+        const uint2 b = ld8(hi + r + 64 * h);
+        sw[h][NS - 2] = b.x, sw[h][NS - 1] = b.y;
+      }
     }
-  };
-  const uint32_t rest_b = __builtin_amdgcn_readfirstlane(fb_rest);
-  for (int64_t t = wave; t < work_tiles; t += nwaves) {
-    uint32_t sw[2][4];
-    load(t, sw);
     __builtin_amdgcn_sched_barrier(0);
-    uint32_t ob[2][4];
+    uint32_t ob[2][NS];
 #pragma unroll
     for (int h = 0; h < 2; h++)
 #pragma unroll
@@ -978,7 +986,7 @@ __global__ __launch_bounds__(1024, 8) void k_bu_fin(const uint2* __restrict__ lo
         else
           ob[h][k] = fin_candidate(w, clo, cr) ? (w >> 3) & bmask : kNoProbe;
       }
-    uint32_t lw[2][4], gw[2][4];
+    uint32_t lw[2][NS], gw[2][NS];
 #pragma unroll
     for (int h = 0; h < 2; h++)
 #pragma unroll
@@ -1018,8 +1026,8 @@ __global__ __launch_bounds__(1024, 8) void k_bu_fin(const uint2* __restrict__ lo
       }
       f[h] = fh;
       // pending: no passing hit, and a hit (then in an undecided bucket) or a fifth entry
-      // (slot 3 set)
-      pend[h] = !fh && (ah || sw[h][3] != 0xffffffffu);
+      // (slot 3 set; never in a two-slot tile)
+      pend[h] = !fh && (ah || (NS == 4 && sw[h][NS - 1] != 0xffffffffu));
     }
     unsigned long long f0 = __ballot(f[0]), f1 = __ballot(f[1]);
     unsigned long long p0 = __ballot(pend[0]), p1 = __ballot(pend[1]);
@@ -1034,6 +1042,26 @@ __global__ __launch_bounds__(1024, 8) void k_bu_fin(const uint2* __restrict__ lo
     nfound += uint64_t(__popcll(f0) + __popcll(f1));
     npend += uint64_t(__popcll(p0) + __popcll(p1));
     nwords += uint64_t(2 * NS) * 64u;
+  };
+  // tile_wide word of tile t (wave-uniform index: a scalar load); past the work tiles it reads
+  // the word of tile work_tiles, at most the bitmap's padding word.  wide == nullptr: all wide.
+  auto wide_word = [&](int64_t t) -> uint32_t {
+    if (!wide) return 0xffffffffu;
+    return wide[__builtin_amdgcn_readfirstlane(uint32_t(min(t, work_tiles) >> 5))];
+  };
+  uint32_t ww = wave < work_tiles ? wide_word(wave) : 0u;
+  for (int64_t t = wave; t < work_tiles; t += nwaves) {
+    // this tile's bit is tested first, then the next tile's word is asked for, ahead of this
+    // tile's work: the wait is then for a load issued a tile ago.  (With the load above the
+    // test the wait stood behind the new load too -- scalar loads return out of order, a wait
+    // is for all of them -- a round trip per tile.)
+    const uint32_t wbit = __builtin_amdgcn_readfirstlane((ww >> (uint32_t(t) & 31u)) & 1u);
+    __builtin_amdgcn_sched_barrier(0);
+    ww = wide_word(t + nwaves);
+    if (wbit)
+      tile(t, std::integral_constant<int, 4>{});
+    else
+      tile(t, std::integral_constant<int, 2>{});
   }
   // tiles past the last row with an in-edge: nothing to find
   for (int64_t t = work_tiles + wave; t < ntiles; t += nwaves)
@@ -2503,6 +2531,7 @@ struct BuLaunch {
   std::string k0, k1;          // rocprof names of the first-pass and the rest-pass kernel
   bool rest_rec = false;       // the rest pass read the rest records
   uint64_t od_bytes = 0;       // out-degree bytes the first pass read (non-final hop)
+  uint64_t flag_bytes = 0;     // tile_wide bytes the first pass read (final hop, bu_fin_narrow)
 };
 BuLaunch launch_bu_lean(Ctx& c, EdgeSpace& es, const uint32_t* fb, uint32_t* nbits, const uint32_t* odeg, int pk,
                       const FastArgs& fp, int fcol, unsigned long long* out, bool hop_front,
@@ -2581,6 +2610,7 @@ BuLaunch launch_bu_lean(Ctx& c, EdgeSpace& es, const uint32_t* fb, uint32_t* nbi
     default: go(k_bu_lean<PKV, 1, 1, 1>); break;     \
   }
   const bool fin = fast && !probe_stats && c.opt("bu_fin", 1) != 0;
+  uint64_t flag_bytes = 0;  // tile_wide words the final first pass read
   char fin_nm[64] = "";
   if (fin) {
     const FinArgs fa = fin_args(q);
@@ -2589,10 +2619,13 @@ BuLaunch launch_bu_lean(Ctx& c, EdgeSpace& es, const uint32_t* fb, uint32_t* nbi
     const size_t fshm = size_t((cw + 2) & ~1) * 4 + size_t(kSlots) * 16 * 8;
     const uint32_t rest = fb_bytes > uint32_t(cw) * 4u ? fb_bytes - uint32_t(cw) * 4u : 0u;
     const int nt = int(c.opt("bu_fin_nt", 1) != 0);
+    // bu_fin_narrow = 0 (A/B runs, tests): every tile reads both halves
+    const uint32_t* wide = c.opt("bu_fin_narrow", 1) != 0 ? es.tile_wide.as<uint32_t>() : nullptr;
+    if (wide) flag_bytes = uint64_t(work) / 8;
     auto gof = [&](auto kern) {
       if (fshm > 48 * 1024) lds_limit(reinterpret_cast<const void*>(kern), fshm);
       kern<<<grid, bs, fshm, c.stream>>>(lo, hi, ntiles, work, fb, nb, pbits, fa, partials, cw, rest, gate, gi,
-                                         atomic_sums);
+                                         atomic_sums, wide);
     };
     switch ((cls1 ? 1 : 0) | nt << 1) {
       case 0: gof(k_bu_fin<0, 0>); break;
@@ -2687,6 +2720,7 @@ BuLaunch launch_bu_lean(Ctx& c, EdgeSpace& es, const uint32_t* fb, uint32_t* nbi
   // the non-final first pass reads one out-degree per row of its work tiles: 1 B (odeg8, the
   // non-temporal instantiations) or 4 B (odeg)
   if (!fast) L.od_bytes = uint64_t(work) * 128u * (sel == 8 ? 1u : 4u);
+  L.flag_bytes = flag_bytes;
   const int wn = fast ? (W == 1 || W == 2 || W == 4 ? W : 8) : 0;
   snprintf(nm, sizeof nm, "nbg::k_bu_rest_lean<%d, %d, %d, %d>", pk, wn, rcw > 0 ? 1 : 0, use_rec ? 1 : 0);
   L.rest_rec = use_rec;
@@ -2697,7 +2731,9 @@ BuLaunch launch_bu_lean(Ctx& c, EdgeSpace& es, const uint32_t* fb, uint32_t* nbi
 // byte models of a bottom-up hop's two passes from their counters.
 // First pass: 4 B per slab word read, the frontier bitmap once, the next-frontier and pending
 // bits written, the out-degrees a non-final hop read (od_bytes: 1 B per work row from odeg8;
-// rounds 2-4 counted 4 B for every row, 1.5x the bytes the default kernel reads).  Rest pass:
+// rounds 2-4 counted 4 B for every row, 1.5x the bytes the default kernel reads) or the
+// tile_wide bits the final hop read (one per work tile; the slab words already count 4 a row
+// for a two-slot tile).  Rest pass:
 // a row_ptr pair (or a 64 B rest record) per pending row, 4 B per entry read, predicate values read.
 uint64_t bu_first_bytes(const unsigned long long* h, int64_t n_rows, uint64_t od_bytes) {
   return h[kHopSlabWords] * 4 + 3 * (uint64_t(n_rows) / 8) + od_bytes;
@@ -3274,7 +3310,7 @@ struct GoQuery {
     c.timing.expand_launches++;
     c.timing.bu_steps++;
     const int pw = final && fpk.kind == PK_FAST ? fp.width : 0;
-    const uint64_t kb = bu_first_bytes(h, es.tr.n_rows, L.od_bytes), hb = kb + bu_rest_bytes(h, pw, L.rest_rec);
+    const uint64_t kb = bu_first_bytes(h, es.tr.n_rows, L.od_bytes + L.flag_bytes), hb = kb + bu_rest_bytes(h, pw, L.rest_rec);
     c.timing.expand_bytes += hb + (final ? uint64_t(es.tr.n_rows) / 8 + uint64_t(out_rows) * 16 : 0);
     c.timing.hop(1, final, 0.0, h, 0.0, kb);
     c.timing.name_last_hop(L.k0, L.k1, final ? "nbg::k_bits_compact<1, 8, 1>" : nullptr);
