@@ -318,6 +318,68 @@ int32_t nbg_shortest_path(nbg_ctx* ctx, int32_t edge_type, const int64_t* src,
 int32_t nbg_order_by(nbg_ctx* ctx, const nbg_rows* in, const int32_t* cols, const int32_t* desc,
                      size_t n_factors, int32_t keep_on_device, nbg_rows* out);
 
+/* ---- UNION / INTERSECT / MINUS -----------------------------------------------------------------
+ * Replaces SetExecutor (src/graph/SetExecutor.cpp:143-328: doUnion / doDistinct's sort + unique,
+ * and the nested row loops of doIntersect / doMinus) on two result tables: `A UNION [ALL|DISTINCT]
+ * B`, `A INTERSECT B`, `A MINUS B`.  left / right: plain row tables as nbg_go / nbg_order_by hand
+ * them out, each one host-resident (uploaded) or device-resident on this context (read in place);
+ * neither is consumed or modified, and the caller frees left, right and out.  A table carrying
+ * row_vertex, vertices, failed parts or paths is NBG_E_INVALID_ARG.
+ * Schema (checkSchema, SetExecutor.cpp:188-218): the column counts must match, else
+ * NBG_E_INVALID_ARG "Field count not match."; a side with n_cols = 0 and n_rows = 0 is the
+ * reference's nullptr result and takes the other side's schema.  The output's column types are the
+ * left's.  VID / INT / TIMESTAMP are one integer type; where the types otherwise differ the right
+ * column is first cast to the left's type (doCasting, SetExecutor.cpp:220-234;
+ * InterimResult::castTo, InterimResult.cpp:215-347): int <-> double by static_cast, int / double ->
+ * bool by != 0, bool -> int / double as 0 / 1.  double -> int of NaN or of a value outside int64 is
+ * undefined in the reference: here it saturates, and NaN becomes 0.  A cast to or from STRING is
+ * NBG_E_UNSUPPORTED.
+ * Row equality (owned by this build, DESIGN.md divergence 9): integers, bools and strings by value
+ * (strings as bytes plus length, embedded NUL bytes legal); doubles under ORDER BY's tie rule:
+ * -0.0 == +0.0 and every NaN equals every NaN (the reference's == never matches a NaN).  An output
+ * row carries the bits of the input row it came from.
+ *   NBG_SET_UNION, distinct = 0   the left rows, then the right rows (after any cast), each side in
+ *                                 input order (doUnion, SetExecutor.cpp:143-186)
+ *   NBG_SET_UNION, distinct = 1   of that concatenation the first occurrence of every distinct row,
+ *                                 in concatenation order.  doDistinct (SetExecutor.cpp:237-241)
+ *                                 leaves the rows sorted; this call does not sort (chain
+ *                                 nbg_order_by over every column for that order).  A side without
+ *                                 rows is an empty set, and the other side is still deduplicated
+ *                                 (the reference returns it as it is, SetExecutor.cpp:145-157)
+ *   NBG_SET_INTERSECT             every left row equal to some right row, in left order, with the
+ *                                 left's multiplicity (doIntersect, SetExecutor.cpp:269-277, moves
+ *                                 matched right rows out and compares against the moved-from rows
+ *                                 afterwards; on tables without duplicates the two agree)
+ *   NBG_SET_MINUS                 every left row equal to no right row, in left order, multiplicity
+ *                                 kept: doMinus (SetExecutor.cpp:283-328)
+ * distinct is ignored for INTERSECT / MINUS, as in the reference.  op outside {1, 2, 3} or distinct
+ * outside {0, 1} is NBG_E_INVALID_ARG.  The output is deterministic: the same inputs give the same
+ * rows in the same order on every run.
+ * out: in HBM when keep_on_device = 1, else on the host (STRING columns as packed bytes + n_rows+1
+ * offsets).  edges_scanned = left's + right's.
+ * NBG_E_UNSUPPORTED: left.n_rows + right.n_rows >= 2^32.
+ * NBG_E_NOMEM: the workspace did not fit; the inputs are untouched.  Per row, besides the output
+ * and a host table's upload: INTERSECT / MINUS 8 B (hash) per left and right row, 16 to 32 B (the
+ * table: 8 B x the power of two >= 2 x rows) per right row and 9 B (keep byte, position, index) per
+ * left row; UNION DISTINCT the concatenated columns plus 8 + 9 + 16 to 32 B per row of both sides;
+ * UNION ALL nothing; a right column under a cast adds its cast copy.
+ * Works on any context (no snapshot needed).  Rank-local: with world_size > 1 each rank combines
+ * the rows it holds and no collective is issued; bringing equal rows to the same rank first stays
+ * with the caller.
+ * nbg_last_timing then reports total_ms (uploads, kernels and the output gather; the copies to the
+ * host behind them are not in it), launches (kernels; a scan counts as one), host_waits and
+ * n_hops = 0.  host_waits: 2 (the fetch of the output row count, and the hand-out) for INTERSECT /
+ * MINUS with left rows and for UNION DISTINCT with rows; 1 (the hand-out) otherwise, where the
+ * count needs no device; plus one per STRING column of a device-resident input with rows (its
+ * byte total).
+ * Engine option "set_hash_bits" (default 64; tests): the row hash is masked to its low k bits, so
+ * 0 makes every row collide.                                                                   */
+#define NBG_SET_UNION 1
+#define NBG_SET_INTERSECT 2
+#define NBG_SET_MINUS 3
+int32_t nbg_set_op(nbg_ctx* ctx, int32_t op, const nbg_rows* left, const nbg_rows* right,
+                   int32_t distinct, int32_t keep_on_device, nbg_rows* out);
+
 /* ---- timing of the last call (HIP events on the engine stream) --------------------------- */
 /* one hop of the last nbg_go: mode 0 = top-down expansion of a frontier list, 1 = bottom-up
  * over the transposed CSR.  c[]: top-down {frontier, entries, next frontier, 0, 0, 0};
@@ -364,7 +426,8 @@ typedef struct {
                              nbg_shortest_path: batches that ran device-driven (the others ran
                              host-driven: option sp_dev = 0, or a list overflow re-ran them)   */
   int32_t launches;       /* nbg_shortest_path: kernel launches of its device-driven batches
-                             (ABI 5); nbg_order_by: its kernel launches; 0 for other calls      */
+                             (ABI 5); nbg_order_by / nbg_set_op: their kernel launches; 0 for
+                             other calls                                                     */
   int32_t comm_calls;     /* collectives this rank issued through its communicator in the last
                              call (ABI 6; comm_ms / comm_calls = the mean time of one on the
                              engine stream, enqueue to completion)                              */

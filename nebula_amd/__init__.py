@@ -9,9 +9,9 @@ from ._lib import NbgError, load  # noqa: F401
 from .engine import (AVG, COUNT, SUM, AddEdgesProcessor, AddEdgesRequest, AddVerticesProcessor,  # noqa: F401
                      AddVerticesRequest, Edge, EdgeKey, ExecResponse, Tag, Vertex, FindPathExecutor, GetNeighborsRequest, GoExecutor,  # noqa: F401
                      GraphSpace, OrderByExecutor, PathResult, PropDef, QueryBoundProcessor, QueryResponse, QueryStatsProcessor,
-                     QueryStatsResponse, RowSet, pack_kv)
+                     QueryStatsResponse, RowSet, SetExecutor, pack_kv)
 
-__all__ = ["GraphSpace", "QueryBoundProcessor", "QueryStatsProcessor", "GoExecutor", "FindPathExecutor", "OrderByExecutor",
+__all__ = ["GraphSpace", "QueryBoundProcessor", "QueryStatsProcessor", "GoExecutor", "FindPathExecutor", "OrderByExecutor", "SetExecutor",
            "PathResult", "GetNeighborsRequest", "PropDef", "QueryResponse", "QueryStatsResponse", "RowSet",
            "NbgError", "expr", "load", "pack_kv", "SUM", "COUNT", "AVG", "AddEdgesProcessor", "AddEdgesRequest",
            "AddVerticesProcessor", "AddVerticesRequest", "Edge", "EdgeKey", "Tag", "Vertex", "ExecResponse"]

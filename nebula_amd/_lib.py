@@ -23,6 +23,7 @@ ERRORS = {
 T_BOOL, T_INT, T_VID, T_FLOAT, T_DOUBLE, T_STRING, T_TIMESTAMP = 1, 2, 3, 4, 5, 6, 21
 OWNER_SOURCE, OWNER_DEST, OWNER_EDGE = 1, 2, 3
 ABI_VERSION = 7  # NBG_ABI_VERSION of include/nebula_amd.h
+SET_UNION, SET_INTERSECT, SET_MINUS = 1, 2, 3  # NBG_SET_* (nbg_set_op)
 
 # every symbol the header declares (tests/test_capi.py checks the .so exports them all)
 EXPORTS = [
@@ -33,7 +34,7 @@ EXPORTS = [
     "nbg_snapshot_gen_rmat", "nbg_snapshot_finalize", "nbg_snapshot_write_part", "nbg_snapshot_commit",
     "nbg_snapshot_info_get",
     "nbg_snapshot_out_degree", "nbg_rows_free", "nbg_get_bound", "nbg_bound_stats", "nbg_go", "nbg_shortest_path",
-    "nbg_order_by", "nbg_last_timing", "nbg_set_option",
+    "nbg_order_by", "nbg_set_op", "nbg_last_timing", "nbg_set_option",
 ]
 
 
@@ -136,6 +137,7 @@ def load(path: str | os.PathLike | None = None):
         "nbg_go": (i32, [vp, C.POINTER(GoSpec), C.POINTER(Rows)]),
         "nbg_shortest_path": (i32, [vp, i32, vp, vp, sz, i32, C.POINTER(Rows)]),
         "nbg_order_by": (i32, [vp, C.POINTER(Rows), vp, vp, sz, i32, C.POINTER(Rows)]),
+        "nbg_set_op": (i32, [vp, i32, C.POINTER(Rows), C.POINTER(Rows), i32, i32, C.POINTER(Rows)]),
         "nbg_last_timing": (i32, [vp, C.POINTER(Timing)]),
         "nbg_set_option": (i32, [vp, C.c_char_p, i64]),
     }

@@ -368,6 +368,17 @@ int32_t nbg_order_by(nbg_ctx* ctx, const nbg_rows* in, const int32_t* cols, cons
   });
 }
 
+int32_t nbg_set_op(nbg_ctx* ctx, int32_t op, const nbg_rows* left, const nbg_rows* right, int32_t distinct,
+                   int32_t keep_on_device, nbg_rows* out) {
+  return guarded(ctx, [&](Ctx& c) {
+    if (!left || !right || !out || left == out || right == out) throw Error(NBG_E_INVALID_ARG, "bad arguments");
+    memset(out, 0, sizeof(*out));
+    const int32_t rc = nbg::set_op_run(c, op, *left, *right, distinct, keep_on_device, out);
+    nbg::timing_resolve(c);
+    return rc;
+  });
+}
+
 int32_t nbg_last_timing(nbg_ctx* ctx, nbg_timing* out) {
   return guarded(ctx, [&](Ctx& c) {
     if (!out) throw Error(NBG_E_INVALID_ARG, "null out");

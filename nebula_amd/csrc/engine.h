@@ -680,6 +680,9 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src, const int64_t*
 // order.hip
 int32_t order_by_run(Ctx& c, const nbg_rows& in, const int32_t* cols, const int32_t* desc, size_t n_factors,
                      int32_t keep_on_device, nbg_rows* out);
+// setops.hip
+int32_t set_op_run(Ctx& c, int32_t op, const nbg_rows& left, const nbg_rows& right, int32_t distinct,
+                   int32_t keep_on_device, nbg_rows* out);
 // comm.cpp
 void comm_alltoallv_bytes(Ctx& c, const void* send, const size_t* send_bytes, const size_t* send_off,
                           void* recv, const size_t* recv_bytes, const size_t* recv_off);

@@ -25,6 +25,14 @@ void exclusive_scan_dev(Ctx& c, const T* in, T* out, int64_t n) {
   NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, in, out, T(0), size_t(n), rocprim::plus<T>(), c.stream));
 }
 
+// the same over bytes (keep flags): out[i] = in[0] + ... + in[i - 1] as uint32
+inline void exclusive_scan_dev(Ctx& c, const uint8_t* in, uint32_t* out, int64_t n) {
+  size_t tb = 0;
+  NBG_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, uint32_t(0), size_t(n), rocprim::plus<uint32_t>(), c.stream));
+  c.ws_tmp.ensure(tb);
+  NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, in, out, uint32_t(0), size_t(n), rocprim::plus<uint32_t>(), c.stream));
+}
+
 // rocprim::select in its two calls (size query, run): in[i] with flags[i] != 0 to out, in order;
 // their count to *cnt (device)
 template <typename In, typename Flags, typename Out>

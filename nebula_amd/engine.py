@@ -455,17 +455,15 @@ class GraphSpace:
         # stays usable as the input of a further order_by
         return RowSet(out, holder=_RowsHandle(self.L, out), raw_strings=raw_strings)
 
-    def order_by(self, table, factors, keep_on_device: bool = False) -> RowSet:
-        """ORDER BY on a result table (nbg_order_by): stable, factor 0 the most significant.
-        `table`: a RowSet (on the host, or an ordered one kept in HBM), or [(NBG_T_*, values)] columns
-        for a synthetic table (STRING values as str or bytes; bytes in give bytes out).
-        `factors`: [(column index, desc)]."""
-        factors = [(int(c), int(d)) for c, d in factors]
+    def _table_rows(self, table, who: str):
+        """A result table as the nbg_rows a table call reads: (rows, keepalive, raw_strings).
+        `table`: a RowSet on the host, a RowSet kept in HBM that still owns its columns, or
+        [(NBG_T_*, values)] columns for a synthetic table (STRING values as str or bytes)."""
         if isinstance(table, RowSet):
             if table.on_device:
                 if table._holder is None or table._holder.rows is None:
-                    raise ValueError("order_by: this device RowSet no longer owns its columns")
-                return self._order_rows(table._holder.rows, factors, keep_on_device)
+                    raise ValueError(f"{who}: this device RowSet no longer owns its columns")
+                return table._holder.rows, table._holder, False
             columns = list(zip(table.types, table.columns))
             n = table.n_rows
         else:
@@ -477,10 +475,10 @@ class GraphSpace:
         types = (C.c_int32 * max(nc, 1))(*[t for t, _ in columns])
         cols = (C.c_void_p * max(nc, 1))()
         offs = (C.POINTER(C.c_int64) * max(nc, 1))()
-        keep = []
+        keep = [types, cols, offs]
         for i, (t, vals) in enumerate(columns):
             if len(vals) != n:
-                raise ValueError(f"order_by: column {i} has {len(vals)} rows, column 0 has {n}")
+                raise ValueError(f"{who}: column {i} has {len(vals)} rows, column 0 has {n}")
             if t == _lib.T_STRING:
                 raw |= any(isinstance(v, (bytes, bytearray)) for v in vals)
                 bs = [v.encode() if isinstance(v, str) else bytes(v) for v in vals]
@@ -510,7 +508,31 @@ class GraphSpace:
             rows.n_vertices = len(table.vertex_ids)
             rows.n_failed = len(table.failed)
             rows.n_vertex_cols = len(table.vertex_columns)
+        return rows, keep, raw
+
+    def order_by(self, table, factors, keep_on_device: bool = False) -> RowSet:
+        """ORDER BY on a result table (nbg_order_by): stable, factor 0 the most significant.
+        `table`: a RowSet (on the host, or an ordered one kept in HBM), or [(NBG_T_*, values)] columns
+        for a synthetic table (STRING values as str or bytes; bytes in give bytes out).
+        `factors`: [(column index, desc)]."""
+        factors = [(int(c), int(d)) for c, d in factors]
+        rows, _keep, raw = self._table_rows(table, "order_by")
         return self._order_rows(rows, factors, keep_on_device, raw_strings=raw)
+
+    def set_op(self, op: int, left, right, distinct: bool = False, keep_on_device: bool = False) -> RowSet:
+        """UNION / INTERSECT / MINUS of two result tables (nbg_set_op); `op`: _lib.SET_UNION /
+        SET_INTERSECT / SET_MINUS.  `left` / `right`: what order_by takes as its table, each one on
+        the host or kept in HBM; neither is changed.  UNION with distinct keeps the first occurrence
+        of every row, in concatenation order (SetExecutor adds the reference's sort)."""
+        lrows, _lkeep, lraw = self._table_rows(left, "set_op")
+        rrows, _rkeep, rraw = self._table_rows(right, "set_op")
+        for t, r in ((left, lrows), (right, rrows)):
+            if isinstance(t, RowSet) and not t.on_device:
+                r.edges_scanned = t.edges_scanned  # (a device table's rows carry theirs)
+        out = _lib.Rows()
+        self._check(self.L.nbg_set_op(self.h, int(op), C.byref(lrows), C.byref(rrows), int(distinct),
+                                      int(bool(keep_on_device)), C.byref(out)))
+        return RowSet(out, holder=_RowsHandle(self.L, out), raw_strings=lraw or rraw)
 
     def shortest_path(self, src, dst, edge_type: int, max_steps: int = 5) -> "PathResult":
         """Pairwise shortest paths (src[i] -> dst[i]) over edge_type out-edges."""
@@ -809,6 +831,28 @@ class OrderByExecutor:
 
     def execute(self, rowset, keep_on_device: bool = False) -> RowSet:
         return self.space.order_by(rowset, self.sort_factors, keep_on_device)
+
+
+class SetExecutor:
+    """A UNION [ALL | DISTINCT] B, A INTERSECT B, A MINUS B (SetExecutor, src/graph/SetExecutor.cpp).
+    `op`: _lib.SET_UNION / SET_INTERSECT / SET_MINUS or "UNION" / "INTERSECT" / "MINUS".  For UNION
+    DISTINCT the deduplicated table stays in HBM and is ordered there by every column ascending, so
+    the response has the order doDistinct's sort + unique leaves (RowValue::operator<)."""
+
+    OPS = {"UNION": _lib.SET_UNION, "INTERSECT": _lib.SET_INTERSECT, "MINUS": _lib.SET_MINUS}
+
+    def __init__(self, space: GraphSpace, op, distinct: bool = False):
+        if isinstance(op, str):
+            if op.upper() not in self.OPS:
+                raise ValueError(f"set operator {op!r}")
+            op = self.OPS[op.upper()]
+        self.space, self.op, self.distinct = space, int(op), bool(distinct)
+
+    def execute(self, left, right, keep_on_device: bool = False) -> RowSet:
+        if self.op == _lib.SET_UNION and self.distinct:
+            rs = self.space.set_op(self.op, left, right, True, keep_on_device=True)
+            return self.space.order_by(rs, [(c, ASC) for c in range(len(rs.types))], keep_on_device)
+        return self.space.set_op(self.op, left, right, self.distinct, keep_on_device)
 
 
 class FindPathExecutor:
