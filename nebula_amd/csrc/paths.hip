@@ -7,27 +7,37 @@
 // among the shortest paths.  The oracle (oracle/refcpu.cpp ora_shortest_path) states it as a
 // backward BFS from dst over the -type in-edge keys followed by a greedy walk from src.
 //
-// Device algorithm, for a batch of B pairs at once (one context = one GPU):
+// Device algorithm, for a batch of B pairs at once (one context = one GPU; DESIGN section 3):
 //  * per side (F = forward from src over the out CSR, B = backward from dst over the in CSR),
-//    pair and owned vertex, a distance byte dist[side][pair * n + row] (0xFF = unseen).  A
-//    claim is a CAS on the 32-bit word holding the byte, so each (side, pair, vertex) enters
-//    exactly one frontier.
+//    pair and vertex, a distance byte (0xFF = unseen), the two sides of a (pair, vertex)
+//    adjacent by default (sp_ilv) so a claim reads both depths in one load.  A device-driven
+//    claim is a plain byte store (a vertex claimed twice in one launch joins the list twice,
+//    which is harmless); a host-driven claim is a CAS on the word holding the byte.
 //  * frontiers are lists of 64-bit tuples (side | pair | level | row) of all pairs together.
 //    Every iteration each active pair expands the side whose frontier has the smaller sum of
-//    (degree + 1), and ONE edge-balanced launch (the GO expansion's LDS tile scheme: 2048
-//    adjacency entries per workgroup, owner found by binary search in LDS) expands the chosen
-//    sides of all pairs; hubs spread over many tiles.
-//  * a claim of a vertex the other side has already seen is a meet.  With depths (f, b) after
-//    that expansion the distance is f + b, and the meet set is exactly the set of vertices at
-//    position f of the shortest paths (any seen-by-both vertex has ds <= f, dt <= b and
-//    ds + dt >= f + b, so ds = f and dt = b).
-//  * path: the backward distances are extended from the meet set toward src over in-edges,
-//    restricted to vertices whose forward distance completes a shortest path (the "sweep");
-//    afterwards every shortest-path vertex carries its exact distance to dst, and one wave per
-//    pair walks from src taking the smallest vid w among out-neighbours with
-//    dist_B(w) = L - i - 1, the oracle's greedy rule.
+//    (degree + 1).  A select launch turns the live lists into an X table of the expanding
+//    tuples cut into 1024-entry chunks; one wave scans one chunk, so hubs spread over the grid.
+//  * before the expansion a meet probe scans the same chunks for a vertex the other side
+//    already holds; a pair that meets skips its expansion.  With depths (f, b) the distance is
+//    f + b, and the meet set is exactly the set of vertices at position f of the shortest
+//    paths (any seen-by-both vertex has ds <= f, dt <= b and ds + dt >= f + b).
+//  * tests "dist[side][pair][v] == l" go through level filters first (per pair 4096 bits a
+//    level held in registers, then a blocked Bloom filter), and only then read the byte.
+//  * path: the sweep extends the backward distances from the meet set toward src, per pair by
+//    pull (in-rows of the level above) or push (out-rows of the forward level), restricted to
+//    vertices whose forward distance completes a shortest path; then every pair walks from src
+//    one step per launch, its current out-row chunked over the grid, taking the smallest vid w
+//    with dist_B(w) = L - i - 1 by atomicMin: the oracle's greedy rule.
 //  * every claimed byte is recorded in an arena and reset after the batch, so the distance
 //    arrays (2 * B * n bytes, HBM-sized) stay allocated and clean across calls.
+//
+// Two drivers run a batch.  Device-driven (k_dv_*, the default): one fixed chain of launches
+// whose kernels read their work sizes from device counters; the step kernels publish each
+// iteration's counters to coherent host memory and the host enqueues iteration i + 1 before it
+// waits on iteration i.  Host-driven (k_sp_*): the host fetches counters, sizes every launch and
+// grows its lists; it is the fallback when a fixed-capacity list overflows, and the whole call
+// when the device-driven path does not apply.  Host side: PathQuery (one call), DevBatch and
+// HostBatch (one batch each), at the end of this file.
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
@@ -69,7 +79,7 @@ struct SpCsr {  // one direction's adjacency over the owned rows
   const uint8_t* row_ok;  // rows whose keys sit outside hash(vid)'s part are invisible
   // min(degree, 65535) per row, 0 where row_ok is 0 (null: off; 65535: read row_ptr): a claim's
   // degree from a 2-byte entry of an array the Infinity Cache holds (66 MB at RMAT-26) instead of
-  // the 16-byte row_ptr pair of a 262 MB array (option sp_deg16)
+  // the 16-byte row_ptr pair of a 262 MB array (always built: PathQuery::deg16)
   const uint16_t* deg16;
 };
 
@@ -487,8 +497,8 @@ __global__ void k_sweep_push_cost(const uint64_t* __restrict__ arena, int64_t na
     wave_add_keyed(push, p, d, go);
   }
 }
-// bias (option sp_push_bias, in 1/16): push when its entries are below pull's x bias / 16 (a push
-// row scan stops at its first hit, so its full degree sum overstates it)
+// bias (in 1/16; the host passes kPushBias16): push when its entries are below pull's x bias / 16
+// (a push row scan stops at its first hit, so its full degree sum overstates it)
 __global__ void k_sweep_choose(const unsigned long long* pull, const unsigned long long* push, int32_t B,
                                int32_t* push_pair, unsigned long long bias16) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1272,6 +1282,11 @@ constexpr int kCh = 1024;                 // adjacency entries per chunk (one wa
 constexpr int kPubW = 64;                 // words per host publish slot (the sequence word last)
 constexpr int kDvStage = 256;             // claims staged per wave and list
 constexpr int kPairLds = 4096;            // pairs per batch whose per-pair tables the selects keep in LDS
+// host-side constants that were options once (the kernels still take them as arguments)
+constexpr unsigned long long kPushBias16 = 16;  // sweep: push when its entries are below pull's x 16 / 16
+constexpr int32_t kPfAgg = 1;                   // k_dv_expand gathers a chunk's pair-filter bits in LDS
+constexpr int kLvBitsLog2Max = 23;              // host-driven level bitmaps: at most 2^23 bits (1 MiB) a level
+constexpr int kPostGrid = 512;                  // blocks of k_dv_post
 // every counter on a 128-byte line of its own (logical counter i at word i * kCS): blocks of a grid
 // ending together add to a line's words one atomic at a time at the memory side (~12 ns each), so
 // counters that shared a line had serialised each other's adds (round 5: 16 counters per line)
@@ -1950,8 +1965,8 @@ __global__ __launch_bounds__(256, OCC) void k_dv_expand(SpDev d, SpState st, SpF
   __shared__ uint64_t s_stage[4][2][kDvStage];
   // per wave, the pair-filter row its current chunk fills: every claim of a chunk is one
   // (side, pair, level), so the chunk's bits are OR-ed here and leave as at most 128 word atomics
-  // over one contiguous 512-byte row (option sp_dv_pf_lds, default 1) instead of one scattered
-  // memory-side atomic per claim
+  // over one contiguous 512-byte row (argument pf_agg; the host passes kPfAgg = 1) instead of one
+  // scattered memory-side atomic per claim
   __shared__ uint32_t s_pf[4][128];
   // a producer overflowed: its tables are incomplete and the host re-runs the batch, so the block
   // expands nothing -- but the probe's claims still go to the arena below, which is the only
@@ -2231,8 +2246,8 @@ __global__ __launch_bounds__(kBlk) void k_dv_post(SpDev d, SpState st, SpCsr gou
 }
 
 // sweep step j: pull (in-rows of the level above, from the current sweep list) or push (out-rows
-// of the forward level k = f - j, from the arena), per pair the side with fewer entries (option
-// sp_push_bias in 1/16: push when its entries are below pull's x bias / 16)
+// of the forward level k = f - j, from the arena), per pair the side with fewer entries (bias16
+// in 1/16, kPushBias16 from the host: push when its entries are below pull's x bias / 16)
 __device__ inline bool dv_push_pair(const SpDev& d, const SpState& st, uint32_t p, int32_t j,
                                     unsigned long long bias16) {
   const int32_t B = st.B;
@@ -2713,31 +2728,141 @@ static int resident_grid(const void* kernel, int block) {
   return cache[kernel] = cus * per;
 }
 
-int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int64_t* dst_all, size_t npairs_all,
-                          int32_t max_steps, nbg_rows* out) {
-  if (!c.finalized) throw Error(NBG_E_STATE, "snapshot not finalized");
-  if (et <= 0) throw Error(NBG_E_INVALID_ARG, "edge type must be > 0 (paths follow out-edges)");
-  if (max_steps > 254) throw Error(NBG_E_UNSUPPORTED, "max_steps above 254");
-  auto it = c.edges.find(et);
-  if (it == c.edges.end()) throw Error(NBG_E_INVALID_ARG, "edge type not in snapshot");
-  EdgeSpace& es = it->second;
-  if (!es.out.row_ptr.p || !es.in.row_ptr.p) throw Error(NBG_E_STATE, "missing CSR");
-  const Csr* cout = &es.out;
-  const Csr* cin = &es.in;
-  int64_t lo = c.owned_lo(), n = std::max<int64_t>(c.owned_hi() - lo, 1);
-  const int64_t* src = src_all;
-  const int64_t* dst = dst_all;
-  size_t npairs = npairs_all;
+namespace {
+
+// Carve's arithmetic without a block: the bytes a layout asks for
+struct CarveSize {
+  size_t bytes = 0;
+  template <typename T>
+  T* take(size_t b) {
+    bytes += (b + 63) & ~size_t(63);
+    return nullptr;
+  }
+};
+// The per-pair workspace of a device-driven batch (W.dv_pair), stated once: through CarveSize it
+// gives the allocation (for the largest batch), through Carve the pieces of a batch of nb pairs.
+template <typename Cv>
+void dv_pair_layout(Cv& cv, int64_t nb, SpDev& d) {
+  d.gs = cv.template take<int32_t>(size_t(nb) * 8);
+  d.cur = cv.template take<int32_t>(size_t(nb) * 4);
+  d.best = cv.template take<long long>(size_t(nb) * 8);
+  d.wcb = cv.template take<int64_t>(size_t(nb) * 8);
+  d.doff = cv.template take<int64_t>(size_t(nb + 8) * 8);
+  d.pull = cv.template take<unsigned long long>(size_t(nb) * kMaxQ * 8);
+  d.push = cv.template take<unsigned long long>(size_t(nb) * kMaxQ * 8);  // adjacent: k_dv_begin clears both in one pass
+}
+
+constexpr size_t kNoEvent = ~size_t(0);
+
+// One nbg_shortest_path call: the validated edge space, this rank's pairs, the batch geometry, the
+// options (each read once), the results, and the phases shortest_path_run calls in order.  A batch
+// runs as a DevBatch (device-driven, k_dv_*) or, when that is off or overflowed, a HostBatch
+// (host-driven, k_sp_*); both append to the result vectors here.
+//
+// Clean / dirty protocol of the state kept across calls:
+//  * c.sp_dirty: the distance bytes may hold claims (they are all 0xFF otherwise).  Set by
+//    size_batch() when it (re)allocates the block and by run_batches() before the first batch;
+//    cleared by size_batch() once it has queued the wipe, and by run_batches() after the last
+//    batch's reset has drained.  Every batch resets its own bytes (DevBatch: the clear launch or
+//    abort(); HostBatch::reset()), so the flag only matters when a call throws in mid-batch: it
+//    stays true, and the next call's size_batch() wipes the whole block.
+//  * W.dv_clean: the device-driven counters and both filters (dv_cnt, dv_pf, dv_gf) are all zero.
+//    Cleared by DevBatch::run() before its first launch and by size_batch() when it finds
+//    sp_dirty (a failed call may have left filter words and counters set too); set by
+//    ensure_capacity() after zero_dv_state(), by finish_and_clear() once the finish launch has
+//    published (it cleared the counters; the queued clear launch zeroes the filters), and by
+//    abort().  A throw in mid-batch leaves it false: the next ensure_capacity() zeroes.
+struct PathQuery {
+  Ctx& c;
+  const int32_t max_steps;
+  nbg_rows* out;
+  Ctx::SpWork& W = c.sp;
+
+  // ---- options, each read once per call ----
+  const int64_t budget = c.opt("sp_mem_mb", 96 * 1024) << 20;  // distance bytes: 2 per pair and vertex
+  const int64_t batch_opt = c.opt("sp_batch", 1024);
+  const int32_t ilv = c.opt("sp_ilv", 1) != 0 ? 1 : 0;
+  const bool probe = c.opt("sp_probe", 1) != 0;
+  const bool dev_opt = c.opt("sp_dev", 1) != 0;
+  // device-driven
+  const int64_t gf_log2 = gf_bits_log2(c.opt("sp_gf_log2", 24));
+  const bool pf_on = c.opt("sp_pf", 1) != 0;
+  const int64_t soft_dv = std::max<int64_t>(c.opt("sp_dv_list", int64_t(8) << 20), 64);
+  const int32_t dv_diag = int32_t(c.opt("sp_dv_diag", 0));
+  const int64_t dv_grid = c.opt("sp_dv_grid", 0);  // scan grids (0: each kernel's resident grid)
+  const int dv_occ = int(c.opt("sp_dv_occ", 1));
+  const int32_t begin_x = c.opt("sp_dv_begin_x", 1) != 0 ? 1 : 0;  // iteration 1's select folded into the batch start
+  // the sweep at 6 waves per SIMD (80 VGPRs, 12 B spilled): C4 1.164 -> 1.140 ms against the
+  // register-bound 5 (8: 64 VGPRs, 76 B spilled, 1.155; 8 entries per lane: 1.211; c4occ)
+  const int sweep_occ = int(c.opt("sp_sweep_occ", 6));
+  // host-driven
+  const int64_t soft = std::max<int64_t>(c.opt("sp_list_soft", int64_t(16) << 20), 1024);
+  const bool lvbits_on = c.opt("sp_lvbits", 1) != 0;
+  const int32_t sweep_mode = c.opt("sp_sweep_src", 0) ? 1 : 2;
+  const bool sweep_push = c.opt("sp_sweep_push", 1) != 0;
+  const bool sweep_chunks = c.opt("sp_sweep_chunks", 1) != 0;
+  const bool walk_wg = c.opt("sp_walk_wg", 0) != 0;
+
+  // ---- validate(), choose_pairs(): this rank's pairs and the CSRs they run over (the replicas when sharded) ----
+  EdgeSpace* es = nullptr;
+  const Csr *cout = nullptr, *cin = nullptr;
+  int64_t lo = 0, n = 1;
+  const int64_t *src = nullptr, *dst = nullptr;
+  size_t npairs = 0;
   std::vector<int64_t> my_src, my_dst;
-  if (c.sharded) {
-    if (!es.has_rep) {
-      if (!es.has_rep_out) replicate_csr(c, es.out, es.rep_out);
-      es.has_rep_out = true;
-      replicate_csr(c, es.in, es.rep_in);
-      es.has_rep = true;
+
+  // ---- size_batch(): pairs per batch, the coherent host block's layout, the result vectors ----
+  int64_t B = 1;
+  bool dev = false;  // batches try the device-driven chain first
+  int64_t dvB = 0;   // pairs the device-driven workspaces are sized for
+  size_t hb_pub = 0, hb_fin = 0, hb_pairs = 0, hb_sr = 0, hb_off = 0, hb_path = 0, hb_end = 0;
+  std::vector<int64_t> hres, hoff = std::vector<int64_t>(1, 0), hpath;
+  std::vector<int32_t> hstate, hside, hmet;  // host-driven: pair_list's copies, the unstaged fetch
+
+  // ---- start(): kernel arguments every batch shares ----
+  uint8_t *d0 = nullptr, *d1 = nullptr;
+  SpCsr gout{}, gin{};
+  const int64_t* const vid_of = c.vid_of.as<int64_t>();
+  const int64_t* const htk = c.ht_keys.as<int64_t>();  // vid -> gidx table
+  const int32_t* const htv = c.ht_vals.as<int32_t>();
+  const uint64_t htm = uint64_t(c.ht_cap - 1);
+
+  // below 2^5 bits: off; at least 2^7 bits otherwise (k_dv_clear zeroes the words 4 at a time)
+  static int64_t gf_bits_log2(int64_t o) {
+    const int64_t lg = std::min<int64_t>(std::max<int64_t>(o, 0), 32);
+    return lg >= 5 ? std::max<int64_t>(lg, 7) : lg;
+  }
+  static Error walk_error() {
+    return Error(NBG_E_UNKNOWN, "shortest path: in-edge keys without mirrored out-edges on a shortest path");
+  }
+
+  void validate(int32_t et) {
+    if (!c.finalized) throw Error(NBG_E_STATE, "snapshot not finalized");
+    if (et <= 0) throw Error(NBG_E_INVALID_ARG, "edge type must be > 0 (paths follow out-edges)");
+    if (max_steps > 254) throw Error(NBG_E_UNSUPPORTED, "max_steps above 254");
+    auto it = c.edges.find(et);
+    if (it == c.edges.end()) throw Error(NBG_E_INVALID_ARG, "edge type not in snapshot");
+    es = &it->second;
+    if (!es->out.row_ptr.p || !es->in.row_ptr.p) throw Error(NBG_E_STATE, "missing CSR");
+  }
+
+  void choose_pairs(const int64_t* src_all, const int64_t* dst_all, size_t npairs_all) {
+    cout = &es->out;
+    cin = &es->in;
+    lo = c.owned_lo();
+    n = std::max<int64_t>(c.owned_hi() - lo, 1);
+    src = src_all;
+    dst = dst_all;
+    npairs = npairs_all;
+    if (!c.sharded) return;
+    if (!es->has_rep) {
+      if (!es->has_rep_out) replicate_csr(c, es->out, es->rep_out);
+      es->has_rep_out = true;
+      replicate_csr(c, es->in, es->rep_in);
+      es->has_rep = true;
     }
-    cout = &es.rep_out;
-    cin = &es.rep_in;
+    cout = &es->rep_out;
+    cin = &es->rep_in;
     lo = 0;
     n = std::max<int64_t>(c.n_global, 1);
     for (size_t i = size_t(c.rank); i < npairs_all; i += size_t(c.world)) {
@@ -2749,50 +2874,60 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
     npairs = my_src.size();
   }
 
-  // batch size: bounded by the distance arrays' HBM budget (2 bytes per pair and vertex)
-  const int64_t budget = c.opt("sp_mem_mb", 96 * 1024) << 20;
-  int64_t B = std::min<int64_t>(c.opt("sp_batch", 1024), std::max<int64_t>(1, budget / (2 * n)));
-  B = std::max<int64_t>(1, std::min<int64_t>(B, std::max<int64_t>(int64_t(npairs), 1)));
-  B = std::min<int64_t>(B, 0x7FFFFF);
-  const size_t dist_bytes = ((size_t(B) * size_t(n) + 3) & ~size_t(3)) + 64;
-  {
-    // both sides' distance arrays in one block of 2 x dist_bytes: side 1 in its upper half, or
-    // (option sp_ilv, default) interleaved with side 0 byte by byte.  Either layout is all 0xFF
-    // between batches, so the option may change from call to call.
-    PoolScope none(nullptr);  // the distance arrays live outside the query pool
-    if (c.sp_dist_bytes < dist_bytes) {
-      for (auto& d : c.sp_dist) d.release();
-      c.sp_dist_bytes = 0;
-      c.sp_dist[0].alloc(2 * dist_bytes);
-      c.sp_dist_bytes = dist_bytes;
-      c.sp_dirty = true;
+  void size_batch() {
+    // batch size: bounded by the distance arrays' HBM budget (2 bytes per pair and vertex)
+    B = std::min<int64_t>(batch_opt, std::max<int64_t>(1, budget / (2 * n)));
+    B = std::max<int64_t>(1, std::min<int64_t>(B, std::max<int64_t>(int64_t(npairs), 1)));
+    B = std::min<int64_t>(B, 0x7FFFFF);
+    const size_t dist_bytes = ((size_t(B) * size_t(n) + 3) & ~size_t(3)) + 64;
+    {
+      // both sides' distance arrays in one block of 2 x dist_bytes: side 1 in its upper half, or
+      // (option sp_ilv, default) interleaved with side 0 byte by byte.  Either layout is all 0xFF
+      // between batches, so the option may change from call to call.
+      PoolScope none(nullptr);  // the distance arrays live outside the query pool
+      if (c.sp_dist_bytes < dist_bytes) {
+        for (auto& d : c.sp_dist) d.release();
+        c.sp_dist_bytes = 0;
+        c.sp_dist[0].alloc(2 * dist_bytes);
+        c.sp_dist_bytes = dist_bytes;
+        c.sp_dirty = true;
+      }
+      if (c.sp_dirty) {
+        wipe_dist();
+        W.dv_clean = false;
+      }
+      c.sp_dirty = false;
     }
-    if (c.sp_dirty) {
-      NBG_HIP(hipMemsetAsync(c.sp_dist[0].p, 0xFF, 2 * c.sp_dist_bytes, c.stream));
-      c.sp.dv_clean = false;  // a failed call may have left filter words and counters set too
+    if (W.cap_state < B) {
+      PoolScope none(nullptr);
+      W.state.alloc(size_t(B) * 48 + 64);
+      W.cnt.alloc(C_N * 8);
+      W.vids.alloc(size_t(B) * 16);
+      W.gidx.alloc(size_t(B) * 8);
+      W.plist.alloc(size_t(B) * 4 + 64);
+      W.cap_state = B;
     }
-    c.sp_dirty = false;
+    // device-driven batches: fixed capacities sized once per context and batch size (pair-major
+    // distance bytes only: the kernels address a pair's bytes from one row pointer)
+    dev = dev_opt && max_steps <= kMaxQ - 2 && lo == 0 && B <= kPairLds;
+    // host block layout (coherent pinned): publish slots, the finish copy of every counter, the
+    // pairs, then the results
+    dvB = std::max<int64_t>(W.dv_B, B);
+    hb_fin = hb_pub + size_t(kMaxQ) * kPubW * 8;
+    hb_pairs = hb_fin + size_t(kDevCnt + 64) * 8;
+    hb_sr = hb_pairs + size_t(dvB) * 16;
+    hb_off = hb_sr + ((size_t(dvB) * 8 + 63) & ~size_t(63));
+    hb_path = hb_off + size_t(dvB + 8) * 8;
+    hb_end = hb_path + size_t(dvB) * (kMaxQ + 1) * 8;
+    hres.resize(npairs);
+    hstate.resize(size_t(2 * B));
+    hside.resize(size_t(B));
+    hmet.resize(size_t(B));
   }
-  Ctx::SpWork& W = c.sp;
-  if (W.cap_state < B) {
-    PoolScope none(nullptr);
-    W.state.alloc(size_t(B) * 48 + 64);
-    W.cnt.alloc(C_N * 8);
-    W.vids.alloc(size_t(B) * 16);
-    W.gidx.alloc(size_t(B) * 8);
-    W.plist.alloc(size_t(B) * 4 + 64);
-    W.cap_state = B;
-  }
-  PoolScope pool_scope(query_pool(c));
-  c.timing = Timing{};
-  c.tev_used = 0;
-  c.hop_timing = c.opt("hop_timing", 1) != 0;  // event pairs around the scan launches (0: none)
-  hipEventRecord(c.ev[0], c.stream);
+  void wipe_dist() { NBG_HIP(hipMemsetAsync(c.sp_dist[0].p, 0xFF, 2 * c.sp_dist_bytes, c.stream)); }
 
-  const int32_t ilv = c.opt("sp_ilv", 1) != 0 ? 1 : 0;
-  uint8_t* d0 = c.sp_dist[0].as<uint8_t>();
-  uint8_t* d1 = ilv ? d0 + 1 : d0 + c.sp_dist_bytes;
-  auto deg16 = [&](int k, const Csr* g) -> const uint16_t* {
+  // min(degree, 65535) of every row of direction k's CSR, rebuilt when that CSR changed
+  const uint16_t* deg16(int k, const Csr* g) {
     if (g->n_rows <= 0) return nullptr;
     if (W.deg16_rp[k] != g->row_ptr.p || W.deg16_rows[k] != g->n_rows || W.deg16_commits[k] != c.commits) {
       PoolScope none(nullptr);  // kept across calls, outside the query pool
@@ -2805,29 +2940,45 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
       W.deg16_commits[k] = c.commits;
     }
     return W.deg16[k].as<uint16_t>();
-  };
-  SpCsr gout{cout->row_ptr.as<int64_t>(), cout->col.as<int32_t>(), cout->row_ok.as<uint8_t>(), deg16(0, cout)};
-  SpCsr gin{cin->row_ptr.as<int64_t>(), cin->col.as<int32_t>(), cin->row_ok.as<uint8_t>(), deg16(1, cin)};
-  const int64_t* vid_of = c.vid_of.as<int64_t>();
-  unsigned long long* cnt = W.cnt.as<unsigned long long>();
-  unsigned long long* hc = c.host_counters;  // pinned
-  int64_t* dsv = W.vids.as<int64_t>();
-  int64_t* dtv = dsv + B;
-  int32_t* dgs = W.gidx.as<int32_t>();
-  int32_t* dgt = dgs + B;
-  const int64_t soft = std::max<int64_t>(c.opt("sp_list_soft", int64_t(16) << 20), 1024);
-  const bool probe = c.opt("sp_probe", 1) != 0;
+  }
 
-  std::vector<int64_t> hres(npairs), hoff(1, 0), hpath;
-  std::vector<int32_t> hstate(static_cast<size_t>(2 * B)), hside(static_cast<size_t>(B)),
-      hmet(static_cast<size_t>(B));
-  // ---- device-driven batches (k_dv_*): fixed capacities sized once per context and batch size;
-  // false = a list overflowed (the clean state is restored, the batch runs host-driven below)
-  // (pair-major distance bytes only: the kernels address a pair's bytes from one row pointer)
-  const bool dev = c.opt("sp_dev", 1) != 0 && max_steps <= kMaxQ - 2 && lo == 0 &&
-                   B <= kPairLds;
-  auto dv_event = [&]() -> size_t {
-    if (!c.hop_timing) return ~size_t(0);
+  void start() {
+    c.timing = Timing{};
+    c.tev_used = 0;
+    c.hop_timing = c.opt("hop_timing", 1) != 0;  // event pairs around the scan launches (0: none)
+    hipEventRecord(c.ev[0], c.stream);
+    d0 = c.sp_dist[0].as<uint8_t>();
+    d1 = ilv ? d0 + 1 : d0 + c.sp_dist_bytes;
+    gout = SpCsr{cout->row_ptr.as<int64_t>(), cout->col.as<int32_t>(), cout->row_ok.as<uint8_t>(), deg16(0, cout)};
+    gin = SpCsr{cin->row_ptr.as<int64_t>(), cin->col.as<int32_t>(), cin->row_ok.as<uint8_t>(), deg16(1, cin)};
+  }
+
+  void run_batches();  // (defined below the two batch drivers)
+
+  void hand_out() {
+    auto h = std::make_unique<HostRows>();
+    for (int k = 0; k < 3; k++) {
+      h->types.push_back(NBG_T_VID);
+      h->host.emplace_back(npairs * 8 + 8);
+      h->str_off.push_back(nullptr);
+    }
+    for (size_t i = 0; i < npairs; i++) {
+      memcpy(h->host[0].data() + i * 8, src + i, 8);
+      memcpy(h->host[1].data() + i * 8, dst + i, 8);
+      memcpy(h->host[2].data() + i * 8, &hres[i], 8);
+    }
+    for (int k = 0; k < 3; k++) h->cols.push_back(h->host[size_t(k)].data());
+    h->path_offsets = std::move(hoff);
+    h->path_vids = std::move(hpath);
+    if (h->path_vids.empty()) h->path_vids.push_back(0);  // non-null pointer for an empty result
+    fill_rows(out, std::move(h), int64_t(npairs), false);
+    out->edges_scanned = c.timing.edges_scanned;
+  }
+
+  // ---- shared by the two batch drivers ----
+  // an event on the stream when hop_timing is on (kNoEvent otherwise); the time between two
+  size_t mark_event() {
+    if (!c.hop_timing) return kNoEvent;
     if (c.tev_used == c.tev.size()) {
       hipEvent_t e;
       NBG_HIP(hipEventCreate(&e));
@@ -2835,41 +2986,109 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
     }
     NBG_HIP(hipEventRecord(c.tev[c.tev_used], c.stream));
     return c.tev_used++;
-  };
-  auto dv_ms = [&](size_t a, size_t b) -> double {
+  }
+  double event_ms(size_t a, size_t b) const {
     float ms = 0;
-    if (a == ~size_t(0) || b == ~size_t(0)) return 0.0;
+    if (a == kNoEvent || b == kNoEvent) return 0.0;
     if (hipEventElapsedTime(&ms, c.tev[a], c.tev[b]) != hipSuccess) return 0.0;
     return ms;
-  };
-  // host block layout (coherent pinned): publish slots, the finish copy of every counter, the
-  // pairs, then the results
-  const int64_t dvB = std::max<int64_t>(W.dv_B, B);
-  const size_t h_pub = 0, h_fin = h_pub + size_t(kMaxQ) * kPubW * 8, h_pairs = h_fin + size_t(kDevCnt + 64) * 8,
-               h_sr = h_pairs + size_t(dvB) * 16, h_off = h_sr + ((size_t(dvB) * 8 + 63) & ~size_t(63)),
-               h_path = h_off + size_t(dvB + 8) * 8, h_end = h_path + size_t(dvB) * (kMaxQ + 1) * 8;
-  auto dv_pair_bytes = [](int64_t nb) {
-    auto r = [](size_t b) { return (b + 63) & ~size_t(63); };
-    const size_t b = size_t(nb);
-    return r(b * 8) + r(b * 4) + r(b * 8) + r(b * 8) + r((b + 8) * 8) + 2 * r(b * kMaxQ * 8);
-  };
-  auto dv_alloc = [&]() {
+  }
+  // One scan launch into nbg_timing: its time, entries and modelled bytes into the totals, and a
+  // hop record (mode 2 = BFS expansion, 3 = meet probe, 4 = sweep, 5 = walk scan) named for its
+  // kernel.  traversal = false (the walk scans): the entries are out-rows of path vertices, not
+  // the traversal's, and stay out of edges_scanned.
+  void launch_record(int32_t mode, const char* kernel, double ms, uint64_t entries, uint64_t bytes,
+                     const unsigned long long (&c8)[8], bool traversal = true) {
+    c.timing.expand_ms += ms;
+    c.timing.expand_launches++;
+    if (traversal) c.timing.edges_scanned += entries;
+    c.timing.expand_bytes += bytes;
+    c.timing.hop(mode, false, ms, c8);
+    c.timing.name_last_hop(kernel);
+  }
+  // A batch's results from its host copies: h_sr = [state nb][res nb], h_off [nb + 1] offsets into
+  // h_path [plen].  The ends of each path are the host's: src (also the whole path of src == dst)
+  // and dst.
+  void append_batch_results(size_t b0, int64_t nb, const int32_t* h_sr, const int64_t* h_off, const int64_t* h_path,
+                            int64_t plen) {
+    const size_t base = hpath.size();
+    hpath.resize(base + size_t(plen));
+    if (plen > 0) memcpy(hpath.data() + base, h_path, size_t(plen) * 8);
+    for (int64_t p = 0; p < nb; p++) {
+      const int32_t L = h_sr[p] == SP_ACTIVE ? -1 : h_sr[nb + p];
+      hres[b0 + size_t(p)] = L;
+      if (L >= 0) {
+        hpath[base + size_t(h_off[p])] = src[b0 + size_t(p)];
+        if (L > 0) hpath[base + size_t(h_off[p] + L)] = dst[b0 + size_t(p)];
+      }
+      hoff.push_back(hoff.back() + h_off[p + 1] - h_off[p]);
+    }
+  }
+};
+
+// One batch on the device-driven chain: run() is false when a list overflowed;
+// the clean state is then restored and the batch runs host-driven.
+struct DevBatch {
+  PathQuery& q;
+  const size_t b0;
+  const int64_t nb;
+  Ctx& c = q.c;
+  Ctx::SpWork& W = q.W;
+  int32_t nl = 0;  // kernel launches of the batch (nbg_timing.launches)
+
+  // ---- bind_args() ----
+  SpState st{};
+  SpFilt f{};
+  SpDev d{};
+  unsigned long long* pub0 = nullptr;  // coherent host: kMaxQ publish slots of kPubW words
+  unsigned long long* fin = nullptr;   // coherent host: the finish copy of every counter
+  int32_t lg_sub = 0;                  // expansion waves per BFS chunk: 256-entry sub-chunks
+  int max_it = 0;
+
+  // ---- bfs() ----
+  std::vector<uint64_t> seq = std::vector<uint64_t>(size_t(kMaxQ), 0);
+  std::vector<std::array<size_t, 3>> evi = std::vector<std::array<size_t, 3>>(size_t(kMaxQ), {kNoEvent, kNoEvent, kNoEvent});
+  int iters = 0;
+  int64_t maxL = 0, maxF = 0;
+
+  // ---- post_sweep_walk() ----
+  std::vector<std::array<size_t, 2>> evs = std::vector<std::array<size_t, 2>>(size_t(kMaxQ), {kNoEvent, kNoEvent});
+  std::vector<std::array<size_t, 2>> evw = evs;
+  int nsw = 0, nwalk = 0;
+
+  bool run() {
+    ensure_capacity();
+    W.dv_clean = false;  // until the batch's finish launch (or abort()) restores it
+    bind_args();
+    if (!bfs()) return abort(false);
+    post_sweep_walk();
+    if (!finish_and_clear()) return false;
+    c.timing.launches += nl;
+    if (fin[D_WALKERR] && !(f.diag & 4)) throw PathQuery::walk_error();
+    launch_records();
+    q.append_batch_results(b0, nb, d.h_sr, d.h_off, d.h_path, d.h_off[nb]);
+    return true;
+  }
+
+  void zero_dv_state() {  // every counter and filter word
+    NBG_HIP(hipMemsetAsync(W.dv_cnt.p, 0, W.dv_cnt.bytes, c.stream));
+    if (W.dv_pf.p) NBG_HIP(hipMemsetAsync(W.dv_pf.p, 0, W.dv_pf.bytes, c.stream));
+    if (W.dv_gf.p) NBG_HIP(hipMemsetAsync(W.dv_gf.p, 0, W.dv_gf.bytes, c.stream));
+  }
+
+  // Lists, chunk tables, per-pair arrays, filters and the host block, kept while the capacities
+  // the options ask for stay the same.
+  void ensure_capacity() {
     // the global filter (2^24 bits): off costs the expansions nothing but lets the pair filters'
     // false positives fetch a distance line each (sweep step 1: 3.4x its byte model, 1.1x with it)
-    // below 2^5 bits: off; at least 2^7 bits otherwise (k_dv_clear zeroes the words 4 at a time)
-    int64_t gf_log2 = std::min<int64_t>(std::max<int64_t>(c.opt("sp_gf_log2", 24), 0), 32);
-    if (gf_log2 >= 5) gf_log2 = std::max<int64_t>(gf_log2, 7);
-    const bool pf_on = c.opt("sp_pf", 1) != 0;
-    const int64_t nnz = std::max(cout->nnz, cin->nnz);
-    const int64_t soft_dv = std::max<int64_t>(c.opt("sp_dv_list", int64_t(8) << 20), 64);
-    const int64_t cap = std::min<int64_t>(soft_dv, 2 * dvB * n + 64);
-    const int64_t cap_ch = cap + nnz / 512 + 64, cap_wch = std::min<int64_t>(soft_dv, dvB * (nnz / kCh + 1)) + 64;
-    if (W.dv_B >= dvB && W.dv_cap == cap && W.dv_cap_ch == cap_ch && W.dv_gf_log2 == gf_log2 && W.dv_pf_on == pf_on &&
-        c.sp_host && c.sp_host_bytes >= h_end) {
-      if (!W.dv_clean) {  // a failed call: every filter word and counter back to zero
-        NBG_HIP(hipMemsetAsync(W.dv_cnt.p, 0, W.dv_cnt.bytes, c.stream));
-        if (W.dv_pf.p) NBG_HIP(hipMemsetAsync(W.dv_pf.p, 0, W.dv_pf.bytes, c.stream));
-        if (W.dv_gf.p) NBG_HIP(hipMemsetAsync(W.dv_gf.p, 0, W.dv_gf.bytes, c.stream));
+    const int64_t gf_log2 = q.gf_log2, dvB = q.dvB;
+    const int64_t nnz = std::max(q.cout->nnz, q.cin->nnz);
+    const int64_t cap = std::min<int64_t>(q.soft_dv, 2 * dvB * q.n + 64);
+    const int64_t cap_ch = cap + nnz / 512 + 64, cap_wch = std::min<int64_t>(q.soft_dv, dvB * (nnz / kCh + 1)) + 64;
+    if (W.dv_B >= dvB && W.dv_cap == cap && W.dv_cap_ch == cap_ch && W.dv_gf_log2 == gf_log2 && W.dv_pf_on == q.pf_on &&
+        c.sp_host && c.sp_host_bytes >= q.hb_end) {
+      if (!W.dv_clean) {  // a failed call
+        zero_dv_state();
         W.dv_clean = true;
       }
       return;
@@ -2879,9 +3098,9 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
     if (c.sp_host) (void)hipHostFree(c.sp_host);
     c.sp_host = nullptr;
     c.sp_host_bytes = 0;
-    NBG_HIP(hipHostMalloc(&c.sp_host, h_end, hipHostMallocCoherent));
-    memset(c.sp_host, 0, h_end);
-    c.sp_host_bytes = h_end;
+    NBG_HIP(hipHostMalloc(&c.sp_host, q.hb_end, hipHostMallocCoherent));
+    memset(c.sp_host, 0, q.hb_end);
+    c.sp_host_bytes = q.hb_end;
     W.dv_cnt = DevBuf();
     W.dv_cnt.alloc(size_t(kDevCnt) * kCS * 8);
     for (auto& b : W.dv_live) {
@@ -2890,206 +3109,169 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
     }
     for (DevBuf* b : {&W.dv_arena, &W.dv_meet, &W.dv_sw[0], &W.dv_sw[1], &W.dv_X, &W.dv_Xcb}) *b = DevBuf();
     W.dv_arena.alloc(size_t(2 * cap) * 8);
-    W.dv_meet.alloc(size_t(cap) * 8);
-    W.dv_sw[0].alloc(size_t(cap) * 8);
-    W.dv_sw[1].alloc(size_t(cap) * 8);
-    W.dv_X.alloc(size_t(cap) * 8);
-    W.dv_Xcb.alloc(size_t(cap) * 8);
+    for (DevBuf* b : {&W.dv_meet, &W.dv_sw[0], &W.dv_sw[1], &W.dv_X, &W.dv_Xcb}) b->alloc(size_t(cap) * 8);
     for (DevBuf* b : {&W.dv_chx, &W.dv_slot, &W.dv_wchx, &W.dv_pair, &W.dv_path, &W.dv_pf, &W.dv_gf}) *b = DevBuf();
     W.dv_chx.alloc(size_t(cap_ch) * 4);
     W.dv_slot.alloc(size_t(cap_ch) * 8);
     W.dv_wchx.alloc(size_t(cap_wch) * 4);
-    // per pair (the layout run_dev carves, each piece rounded up to 64 bytes): gs [2B] i32, cur [B]
-    // i32, best [B] i64, wcb [B] i64, doff [B + 8] i64, pull [kMaxQ][B] u64, push [kMaxQ][B] u64
-    W.dv_pair.alloc(dv_pair_bytes(dvB));
+    CarveSize pair_bytes;
+    SpDev sized{};
+    dv_pair_layout(pair_bytes, dvB, sized);
+    W.dv_pair.alloc(pair_bytes.bytes);
     W.dv_path.alloc(size_t(dvB) * (kMaxQ + 1) * 8);
-    if (pf_on) W.dv_pf.alloc(size_t(2 * kLv) * size_t(dvB) * 512);
+    if (q.pf_on) W.dv_pf.alloc(size_t(2 * kLv) * size_t(dvB) * 512);
     if (gf_log2 >= 5) W.dv_gf.alloc(size_t(1) << (gf_log2 - 3));
-    NBG_HIP(hipMemsetAsync(W.dv_cnt.p, 0, W.dv_cnt.bytes, c.stream));
-    if (W.dv_pf.p) NBG_HIP(hipMemsetAsync(W.dv_pf.p, 0, W.dv_pf.bytes, c.stream));
-    if (W.dv_gf.p) NBG_HIP(hipMemsetAsync(W.dv_gf.p, 0, W.dv_gf.bytes, c.stream));
+    zero_dv_state();
     W.dv_B = dvB;
     W.dv_cap = cap;
     W.dv_cap_ch = cap_ch;
     W.dv_cap_wch = cap_wch;
     W.dv_gf_log2 = gf_log2;
-    W.dv_pf_on = pf_on;
+    W.dv_pf_on = q.pf_on;
     W.dv_clean = true;
-  };
-  auto run_dev = [&](size_t b0, int64_t nb) -> bool {
-    int32_t nl = 0;  // kernel launches of the batch (nbg_timing.launches)
-    dv_alloc();
-    W.dv_clean = false;  // until the batch's finish launch (or the abort below) restores it
+  }
+
+  // SpState / SpFilt / SpDev of this batch from the workspaces; the pairs into the host block
+  void bind_args() {
     char* hb = static_cast<char*>(c.sp_host);
-    SpState st{};
     st.B = int32_t(nb);
     sp_state_carve(W.state, nb, st);
-    st.ilv = ilv;
-    SpFilt f{};
+    st.ilv = q.ilv;
     f.pf = W.dv_pf.as<uint32_t>();
     f.gf = W.dv_gf.as<uint32_t>();
     f.gshift = W.dv_gf.p ? uint32_t(64 - (W.dv_gf_log2 - 5)) : 0u;
     f.B = int32_t(nb);
-    f.diag = int32_t(c.opt("sp_dv_diag", 0));
-    SpDev d{};
+    f.diag = q.dv_diag;
     d.cnt = W.dv_cnt.as<unsigned long long>();
     for (int k = 0; k < 4; k++) d.live[k >> 1][k & 1] = W.dv_live[k].as<uint64_t>();
-    d.cap_live = W.dv_cap;
+    d.cap_live = d.cap_meet = d.cap_sw = d.cap_x = W.dv_cap;
     d.arena = W.dv_arena.as<uint64_t>();
     d.cap_arena = 2 * W.dv_cap;
     d.meet = W.dv_meet.as<uint64_t>();
-    d.cap_meet = W.dv_cap;
     d.sw[0] = W.dv_sw[0].as<uint64_t>();
     d.sw[1] = W.dv_sw[1].as<uint64_t>();
-    d.cap_sw = W.dv_cap;
     d.X = W.dv_X.as<uint64_t>();
     d.Xcb = W.dv_Xcb.as<int64_t>();
-    d.cap_x = W.dv_cap;
     d.chx = W.dv_chx.as<int32_t>();
     d.slot = W.dv_slot.as<uint64_t>();
     d.cap_ch = W.dv_cap_ch;
     d.wchx = W.dv_wchx.as<int32_t>();
     d.cap_wch = W.dv_cap_wch;
-    {
-      Carve cv(W.dv_pair, "shortest path: per-pair workspace");
-      d.gs = cv.take<int32_t>(size_t(nb) * 8);
-      d.cur = cv.take<int32_t>(size_t(nb) * 4);
-      d.best = cv.take<long long>(size_t(nb) * 8);
-      d.wcb = cv.take<int64_t>(size_t(nb) * 8);
-      d.doff = cv.take<int64_t>(size_t(nb + 8) * 8);
-      d.pull = cv.take<unsigned long long>(size_t(nb) * kMaxQ * 8);
-      d.push = cv.take<unsigned long long>(size_t(nb) * kMaxQ * 8);  // adjacent: k_dv_begin clears both in one pass
-    }
+    Carve cv(W.dv_pair, "shortest path: per-pair workspace");
+    dv_pair_layout(cv, nb, d);
     d.path = W.dv_path.as<int64_t>();
     d.lg_chb = 10;  // 1024-entry chunks
     d.lg_chs = 10;
-    int64_t* hp = reinterpret_cast<int64_t*>(hb + h_pairs);
-    memcpy(hp, src + b0, size_t(nb) * 8);
-    memcpy(hp + nb, dst + b0, size_t(nb) * 8);
+    int64_t* hp = reinterpret_cast<int64_t*>(hb + q.hb_pairs);
+    memcpy(hp, q.src + b0, size_t(nb) * 8);
+    memcpy(hp + nb, q.dst + b0, size_t(nb) * 8);
     d.h_pairs = hp;
-    d.h_sr = reinterpret_cast<int32_t*>(hb + h_sr);
-    d.h_off = reinterpret_cast<int64_t*>(hb + h_off);
-    d.h_path = reinterpret_cast<int64_t*>(hb + h_path);
-    auto pub = [&](int it) { return reinterpret_cast<unsigned long long*>(hb + h_pub) + size_t(it) * kPubW; };
-    unsigned long long* fin = reinterpret_cast<unsigned long long*>(hb + h_fin);
+    d.h_sr = reinterpret_cast<int32_t*>(hb + q.hb_sr);
+    d.h_off = reinterpret_cast<int64_t*>(hb + q.hb_off);
+    d.h_path = reinterpret_cast<int64_t*>(hb + q.hb_path);
+    pub0 = reinterpret_cast<unsigned long long*>(hb + q.hb_pub);
+    fin = reinterpret_cast<unsigned long long*>(hb + q.hb_fin);
+    lg_sub = std::max<int32_t>(0, d.lg_chb - 8);
+    max_it = std::min<int>(q.max_steps, kMaxQ - 2);
+  }
+  unsigned long long* pub(int it) const { return pub0 + size_t(it) * kPubW; }
+  // scan grids: option sp_dv_grid, else each kernel's resident grid
+  int scan_grid(const void* k) const { return q.dv_grid > 0 ? int(q.dv_grid) : resident_grid(k, 256); }
+  // the meet probe at 5 blocks per CU (its resident 8 ran the third iteration at 0.29 ms, 5: 0.22)
+  int probe_grid(const void* k) const {
+    return q.dv_grid > 0 ? int(q.dv_grid) : std::min(resident_grid(k, 256), 5 * cu_count());
+  }
 
-    auto gsel = [&](const void* k) { return resident_grid(k, kBlk); };
-    // scan grids: option sp_dv_grid, else each kernel's resident grid
-    const int64_t grid_opt = c.opt("sp_dv_grid", 0);
-    auto gsz = [&](const void* k) { return grid_opt > 0 ? int(grid_opt) : resident_grid(k, 256); };
-    // the meet probe at 5 blocks per CU (its resident 8 ran the third iteration at 0.29 ms, 5: 0.22)
-    auto gpr = [&](const void* k) {
-      return grid_opt > 0 ? int(grid_opt) : std::min(resident_grid(k, 256), 5 * cu_count());
-    };
-    const int occ = int(c.opt("sp_dv_occ", 1));
-    const int32_t pf_agg = 1;
-    // expansion waves per BFS chunk: 256-entry sub-chunks
-    const int32_t lg_sub = std::max<int32_t>(0, d.lg_chb - 8);
-    const int max_it = std::min<int>(max_steps, kMaxQ - 2);
-    const int64_t htm = int64_t(c.ht_cap - 1);
-    const int64_t* htk = c.ht_keys.as<int64_t>();
-    const int32_t* htv = c.ht_vals.as<int32_t>();
-    std::vector<uint64_t> seq(size_t(kMaxQ), 0);
-    std::vector<std::array<size_t, 3>> evi(size_t(kMaxQ), {~size_t(0), ~size_t(0), ~size_t(0)});
-    std::vector<std::array<size_t, 2>> evs(size_t(kMaxQ), {~size_t(0), ~size_t(0)});
-    std::vector<std::array<size_t, 2>> evw(size_t(kMaxQ), {~size_t(0), ~size_t(0)});
-
-    // the state is restored from whatever the device reached: the claimed bytes from the arena
-    // (wholesale when it overflowed, or `wipe`), every filter word and counter cleared; the batch
-    // then runs host-driven
-    auto dv_abort = [&](bool wipe) {
-      NBG_HIP(hipStreamSynchronize(c.stream));
-      unsigned long long na = 0;
-      NBG_HIP(hipMemcpy(&na, gcnt(d.cnt, D_ARENA), 8, hipMemcpyDeviceToHost));
-      if (!wipe && int64_t(na) <= d.cap_arena) {
-        if (na) k_sp_clear<<<grid_n(int64_t(na)), 256, 0, c.stream>>>(d.arena, int64_t(na), d0, d1, n, st);
-      } else {
-        NBG_HIP(hipMemsetAsync(c.sp_dist[0].p, 0xFF, 2 * c.sp_dist_bytes, c.stream));
-      }
-      NBG_HIP(hipMemsetAsync(W.dv_cnt.p, 0, W.dv_cnt.bytes, c.stream));
-      if (W.dv_pf.p) NBG_HIP(hipMemsetAsync(W.dv_pf.p, 0, W.dv_pf.bytes, c.stream));
-      if (W.dv_gf.p) NBG_HIP(hipMemsetAsync(W.dv_gf.p, 0, W.dv_gf.bytes, c.stream));
-      NBG_HIP(hipGetLastError());
-      NBG_HIP(hipStreamSynchronize(c.stream));
-      W.dv_clean = true;
-      return false;
-    };
-
+  // select, meet probe, expansion, step of BFS iteration it
+  void enqueue_iteration(int it) {
+    const int64_t n = q.n, lo = q.lo;
+    if (it > 1 || !q.begin_x) {
+      ++nl;
+      // (at 6 / 8 waves per SIMD, 104 / 176 B spilled: C4 1.133-1.154 -> 1.176-1.197 ms, c4occ3)
+      k_dv_select<<<resident_grid((const void*)k_dv_select, kBlk), kBlk, 0, c.stream>>>(d, st, q.gout, q.gin, it);
+    }
+    evi[size_t(it)][0] = q.mark_event();
+    if (q.probe) {
+      ++nl;
+      // 4 entries per lane and step (8 / 16 measured slower: 0.50 -> 0.70 ms, round 3)
+      k_dv_probe<4><<<probe_grid((const void*)k_dv_probe<4>), 256, 0, c.stream>>>(d, st, f, q.gout, q.gin, q.d0, q.d1, n,
+                                                                                  lo, it);
+    }
+    evi[size_t(it)][1] = q.mark_event();
     ++nl;
-    // iteration 1's select folded into the batch start (option sp_dv_begin_x)
-    const int32_t sel1 = c.opt("sp_dv_begin_x", 1) != 0 ? 1 : 0;
-    k_dv_begin<<<std::max(grid_n(nb, 1 << 20), 64), 256, 0, c.stream>>>(d, st, gout, gin, d0, d1, n, max_steps, htk, htv,
-                                                          uint64_t(htm), c.ht_has_min, c.ht_min_gidx, sel1);
-    auto enqueue = [&](int it) {
-      if (it > 1 || !sel1) {
-        ++nl;
-        // (at 6 / 8 waves per SIMD, 104 / 176 B spilled: C4 1.133-1.154 -> 1.176-1.197 ms, c4occ3)
-        k_dv_select<<<gsel((const void*)k_dv_select), kBlk, 0, c.stream>>>(d, st, gout, gin, it);
-      }
-      evi[size_t(it)][0] = dv_event();
-      if (probe) {
-        ++nl;
-        // 4 entries per lane and step (8 / 16 measured slower: 0.50 -> 0.70 ms, round 3)
-        k_dv_probe<4><<<gpr((const void*)k_dv_probe<4>), 256, 0, c.stream>>>(d, st, f, gout, gin, d0, d1, n, lo, it);
-      }
-      evi[size_t(it)][1] = dv_event();
-      ++nl;
-      if (occ >= 8)
-        k_dv_expand<8><<<gsz((const void*)k_dv_expand<8>), 256, 0, c.stream>>>(d, st, f, gout, gin, d0, d1, n, lo, it,
-                                                                               lg_sub, pf_agg);
-      else
-        k_dv_expand<1><<<gsz((const void*)k_dv_expand<1>), 256, 0, c.stream>>>(d, st, f, gout, gin, d0, d1, n, lo, it,
-                                                                               lg_sub, pf_agg);
-      evi[size_t(it)][2] = dv_event();
-      seq[size_t(it)] = ++c.pub_seq;
-      ++nl;
-      k_dv_step<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(d, st, max_steps, it, pub(it), seq[size_t(it)]);
-      NBG_HIP(hipGetLastError());
-    };
-    enqueue(1);
+    if (q.dv_occ >= 8)
+      k_dv_expand<8><<<scan_grid((const void*)k_dv_expand<8>), 256, 0, c.stream>>>(d, st, f, q.gout, q.gin, q.d0, q.d1, n,
+                                                                                   lo, it, lg_sub, kPfAgg);
+    else
+      k_dv_expand<1><<<scan_grid((const void*)k_dv_expand<1>), 256, 0, c.stream>>>(d, st, f, q.gout, q.gin, q.d0, q.d1, n,
+                                                                                   lo, it, lg_sub, kPfAgg);
+    evi[size_t(it)][2] = q.mark_event();
+    seq[size_t(it)] = ++c.pub_seq;
+    ++nl;
+    k_dv_step<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(d, st, q.max_steps, it, pub(it), seq[size_t(it)]);
+    NBG_HIP(hipGetLastError());
+  }
+
+  // The batch start and the BFS: iteration it + 1 is enqueued before the host waits on iteration
+  // it's counters.  False: a list overflowed.
+  bool bfs() {
+    ++nl;
+    k_dv_begin<<<std::max(grid_n(nb, 1 << 20), 64), 256, 0, c.stream>>>(d, st, q.gout, q.gin, q.d0, q.d1, q.n, q.max_steps,
+                                                                        q.htk, q.htv, q.htm, c.ht_has_min, c.ht_min_gidx,
+                                                                        q.begin_x);
+    enqueue_iteration(1);
     int it = 1;
     for (;; it++) {
-      if (it < max_it) enqueue(it + 1);  // speculative: a no-op when iteration it ends the BFS
+      if (it < max_it) enqueue_iteration(it + 1);  // speculative: a no-op when iteration it ends the BFS
       wait_host_word(c, pub(it) + kPubW - 1, seq[size_t(it)]);
       const unsigned long long* hs = pub(it);
-      if (hs[D_OVF]) return dv_abort(false);
+      if (hs[D_OVF]) return false;
       if (hs[D_G + Q_ACTIVE] == 0 || it >= max_it) break;
     }
-    const int64_t maxL = int64_t(pub(it)[D_MAXL]), maxF = int64_t(pub(it)[D_MAXF]);
-    const int iters = it;
+    maxL = int64_t(pub(it)[D_MAXL]);
+    maxF = int64_t(pub(it)[D_MAXF]);
+    iters = it;
+    return true;
+  }
+
+  // the post pass, every sweep step and every walk step, enqueued in one go
+  void post_sweep_walk() {
+    const int64_t n = q.n, lo = q.lo;
     ++nl;
-    k_dv_post<<<int(std::max<int64_t>(1, 512)), kBlk, 0, c.stream>>>(
-        d, st, gout, gin, lo, htk, htv, uint64_t(htm), c.ht_has_min, c.ht_min_gidx);
-    const int nsw = int(std::min<int64_t>(std::max<int64_t>(maxF - 1, 0), kMaxQ - 2));
-    const unsigned long long bias16 = (unsigned long long)std::max<int64_t>(0, 16);
-    // the sweep at 6 waves per SIMD (80 VGPRs, 12 B spilled): C4 1.164 -> 1.140 ms against the
-    // register-bound 5 (8: 64 VGPRs, 76 B spilled, 1.155; 8 entries per lane: 1.211; c4occ)
-    const int sw_occ = int(c.opt("sp_sweep_occ", 6));
+    k_dv_post<<<kPostGrid, kBlk, 0, c.stream>>>(d, st, q.gout, q.gin, lo, q.htk, q.htv, q.htm, c.ht_has_min,
+                                                c.ht_min_gidx);
+    nsw = int(std::min<int64_t>(std::max<int64_t>(maxF - 1, 0), kMaxQ - 2));
     for (int j = 1; j <= nsw; j++) {
       ++nl;
-      k_dv_sweep_select<<<gsel((const void*)k_dv_sweep_select), kBlk, 0, c.stream>>>(d, st, gout, gin, j, bias16);
-      evs[size_t(j)][0] = dv_event();
+      k_dv_sweep_select<<<resident_grid((const void*)k_dv_sweep_select, kBlk), kBlk, 0, c.stream>>>(d, st, q.gout, q.gin, j,
+                                                                                                    kPushBias16);
+      evs[size_t(j)][0] = q.mark_event();
       ++nl;
-      switch (sw_occ) {
-        case 6: k_dv_sweep<4, 6><<<gsz((const void*)k_dv_sweep<4, 6>), 256, 0, c.stream>>>(d, st, f, gout, gin, d0, d1, n, lo, j); break;
-        case 8: k_dv_sweep<4, 8><<<gsz((const void*)k_dv_sweep<4, 8>), 256, 0, c.stream>>>(d, st, f, gout, gin, d0, d1, n, lo, j); break;
-        case 2: k_dv_sweep<8, 1><<<gsz((const void*)k_dv_sweep<8, 1>), 256, 0, c.stream>>>(d, st, f, gout, gin, d0, d1, n, lo, j); break;
-        default: k_dv_sweep<4><<<gsz((const void*)k_dv_sweep<4>), 256, 0, c.stream>>>(d, st, f, gout, gin, d0, d1, n, lo, j);
+      switch (q.sweep_occ) {
+        case 6: k_dv_sweep<4, 6><<<scan_grid((const void*)k_dv_sweep<4, 6>), 256, 0, c.stream>>>(d, st, f, q.gout, q.gin, q.d0, q.d1, n, lo, j); break;
+        case 8: k_dv_sweep<4, 8><<<scan_grid((const void*)k_dv_sweep<4, 8>), 256, 0, c.stream>>>(d, st, f, q.gout, q.gin, q.d0, q.d1, n, lo, j); break;
+        case 2: k_dv_sweep<8, 1><<<scan_grid((const void*)k_dv_sweep<8, 1>), 256, 0, c.stream>>>(d, st, f, q.gout, q.gin, q.d0, q.d1, n, lo, j); break;
+        default: k_dv_sweep<4><<<scan_grid((const void*)k_dv_sweep<4>), 256, 0, c.stream>>>(d, st, f, q.gout, q.gin, q.d0, q.d1, n, lo, j);
       }
-      evs[size_t(j)][1] = dv_event();
+      evs[size_t(j)][1] = q.mark_event();
     }
-    const int nwalk = int(std::min<int64_t>(maxL >= 2 ? maxL - 1 : 0, kMaxQ - 2));
+    nwalk = int(std::min<int64_t>(maxL >= 2 ? maxL - 1 : 0, kMaxQ - 2));
     for (int i = 0; i < nwalk; i++) {
       if (i > 0) {
         ++nl;
-        k_dv_walk_front<<<grid_n(nb, 1 << 20), kBlk, 0, c.stream>>>(d, st, gout, i, lo, htk, htv, uint64_t(htm),
-                                                                   c.ht_has_min, c.ht_min_gidx);
+        k_dv_walk_front<<<grid_n(nb, 1 << 20), kBlk, 0, c.stream>>>(d, st, q.gout, i, lo, q.htk, q.htv, q.htm, c.ht_has_min,
+                                                                   c.ht_min_gidx);
       }
-      evw[size_t(i)][0] = dv_event();
+      evw[size_t(i)][0] = q.mark_event();
       ++nl;
-      k_dv_walk_scan<<<gsz((const void*)k_dv_walk_scan), 256, 0, c.stream>>>(d, st, f, gout, d1, vid_of, n, lo, i);
-      evw[size_t(i)][1] = dv_event();
+      k_dv_walk_scan<<<scan_grid((const void*)k_dv_walk_scan), 256, 0, c.stream>>>(d, st, f, q.gout, q.d1, q.vid_of, n, lo, i);
+      evw[size_t(i)][1] = q.mark_event();
     }
+  }
+
+  // Results to the host, every counter copied and cleared, the bytes and filters reset; one host
+  // wait.  False: a sweep or walk list overflowed after the BFS.
+  bool finish_and_clear() {
     ++nl;
     k_dv_out<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(d, st, nwalk - 1);
     const uint64_t fseq = ++c.pub_seq;
@@ -3098,111 +3280,250 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
     ++nl;
     k_dv_finish<<<1, 64, 0, c.stream>>>(d.cnt, fin, fin + kDevCnt + 8, fseq, nbfs, nsw, nwalk);
     ++nl;
-    k_dv_clear<<<gsz((const void*)k_dv_clear), 256, 0, c.stream>>>(d, st, f, d0, d1, n);
+    k_dv_clear<<<scan_grid((const void*)k_dv_clear), 256, 0, c.stream>>>(d, st, f, q.d0, q.d1, q.n);
     NBG_HIP(hipGetLastError());
     wait_host_word(c, fin + kDevCnt + 8, fseq);
     W.dv_clean = true;  // the finish launch cleared the counters, the clear launch (queued) the bytes and filters
-    if (fin[D_OVF]) {
-      // a sweep or walk list overflowed after the BFS: the result pass reset every byte and
-      // filter word the arena holds, unless the arena itself overflowed
-      if (int64_t(fin[D_ARENA]) > d.cap_arena) return dv_abort(true);
-      return false;
-    }
-    c.timing.launches += nl;
-    if (fin[D_WALKERR] && !(f.diag & 4))
-      throw Error(NBG_E_UNKNOWN, "shortest path: in-edge keys without mirrored out-edges on a shortest path");
+    if (!fin[D_OVF]) return true;
+    // the result pass reset every byte and filter word the arena holds, unless the arena itself
+    // overflowed
+    if (int64_t(fin[D_ARENA]) > d.cap_arena) return abort(true);
+    return false;
+  }
 
-    // per-launch records (modes 3 = meet probe, 2 = BFS expansion, 4 = sweep), from the copy of
-    // every counter the finish launch made
-    auto blkq = [&](int q) { return fin + D_G + size_t(q) * Q_W; };
+  // The state is restored from whatever the device reached: the claimed bytes from the arena
+  // (wholesale when it overflowed, or `wipe`), every filter word and counter cleared; the batch
+  // then runs host-driven.  Always false (run()'s result).
+  bool abort(bool wipe) {
+    NBG_HIP(hipStreamSynchronize(c.stream));
+    unsigned long long na = 0;
+    NBG_HIP(hipMemcpy(&na, gcnt(d.cnt, D_ARENA), 8, hipMemcpyDeviceToHost));
+    if (!wipe && int64_t(na) <= d.cap_arena) {
+      if (na) k_sp_clear<<<grid_n(int64_t(na)), 256, 0, c.stream>>>(d.arena, int64_t(na), q.d0, q.d1, q.n, st);
+    } else {
+      q.wipe_dist();
+    }
+    zero_dv_state();
+    NBG_HIP(hipGetLastError());
+    NBG_HIP(hipStreamSynchronize(c.stream));
+    W.dv_clean = true;
+    return false;
+  }
+
+  // per-launch records from the copy of every counter the finish launch made
+  // c8 = {X tuples, entries, claims, meets, iteration / step, active pairs, diag, diag}
+  void launch_records() {
+    auto blkq = [&](int k) { return fin + D_G + size_t(k) * Q_W; };
     if (c.hop_timing && c.tev_used) (void)hipEventSynchronize(c.tev[c.tev_used - 1]);
     for (int i = 1; i <= iters; i++) {
-      const unsigned long long* q = blkq(i);
+      const unsigned long long* b = blkq(i);
       const unsigned long long act = blkq(i - 1)[Q_ACTIVE];
       if (act == 0) continue;
       c.timing.steps_run++;
-      const double pms = dv_ms(evi[size_t(i)][0], evi[size_t(i)][1]), ems = dv_ms(evi[size_t(i)][1], evi[size_t(i)][2]);
-      if (probe && q[Q_X]) {
-        c.timing.expand_ms += pms;
-        c.timing.expand_launches++;
-        c.timing.edges_scanned += q[Q_PE];
-        c.timing.expand_bytes += q[Q_X] * 24 + q[Q_PE] * 5;
+      if (q.probe && b[Q_X]) {
         // (diag bit 3: c[2] distance bytes read, c[6] pair-filter passes, c[7] bytes at the depth)
-        const unsigned long long c8[8] = {q[Q_X], q[Q_PE], q[Q_W - 2], fin[D_MEET], (unsigned long long)i, act,
-                                          q[Q_W - 3], q[Q_W - 1]};
-        c.timing.hop(3, false, pms, c8);
-        c.timing.name_last_hop("nbg::(anonymous namespace)::k_dv_probe");
+        const unsigned long long c8[8] = {b[Q_X], b[Q_PE], b[Q_W - 2], fin[D_MEET], (unsigned long long)i, act,
+                                          b[Q_W - 3], b[Q_W - 1]};
+        q.launch_record(3, "nbg::(anonymous namespace)::k_dv_probe", q.event_ms(evi[size_t(i)][0], evi[size_t(i)][1]),
+                        b[Q_PE], b[Q_X] * 24 + b[Q_PE] * 5, c8);
       }
-      if (q[Q_EE]) {
-        c.timing.expand_ms += ems;
-        c.timing.expand_launches++;
-        c.timing.edges_scanned += q[Q_EE];
-        c.timing.expand_bytes += q[Q_X] * 32 + q[Q_EE] * 5 + q[Q_CLAIMS] * 26;
-        const unsigned long long c8[8] = {q[Q_X], q[Q_EE], q[Q_CLAIMS], fin[D_MEET], (unsigned long long)i, act, 0, 0};
-        c.timing.hop(2, false, ems, c8);
-        c.timing.name_last_hop("nbg::(anonymous namespace)::k_dv_expand");
+      if (b[Q_EE]) {
+        const unsigned long long c8[8] = {b[Q_X], b[Q_EE], b[Q_CLAIMS], fin[D_MEET], (unsigned long long)i, act, 0, 0};
+        q.launch_record(2, "nbg::(anonymous namespace)::k_dv_expand", q.event_ms(evi[size_t(i)][1], evi[size_t(i)][2]),
+                        b[Q_EE], b[Q_X] * 32 + b[Q_EE] * 5 + b[Q_CLAIMS] * 26, c8);
       }
     }
     for (int j = 1; j <= nsw; j++) {
-      const unsigned long long* q = blkq(kSwQ + j);
-      if (!q[Q_EE]) continue;
-      const double sms = dv_ms(evs[size_t(j)][0], evs[size_t(j)][1]);
-      c.timing.expand_ms += sms;
-      c.timing.expand_launches++;
-      c.timing.edges_scanned += q[Q_EE];
-      c.timing.expand_bytes += q[Q_X] * 32 + q[Q_EE] * 6 + q[Q_CLAIMS] * 18;
-      const unsigned long long c8[8] = {q[Q_X], q[Q_EE], q[Q_CLAIMS], fin[D_MEET], (unsigned long long)j, 0, 0, 0};
-      c.timing.hop(4, false, sms, c8);
-      c.timing.name_last_hop("nbg::(anonymous namespace)::k_dv_sweep");
+      const unsigned long long* b = blkq(kSwQ + j);
+      if (!b[Q_EE]) continue;
+      const unsigned long long c8[8] = {b[Q_X], b[Q_EE], b[Q_CLAIMS], fin[D_MEET], (unsigned long long)j, 0, 0, 0};
+      q.launch_record(4, "nbg::(anonymous namespace)::k_dv_sweep", q.event_ms(evs[size_t(j)][0], evs[size_t(j)][1]),
+                      b[Q_EE], b[Q_X] * 32 + b[Q_EE] * 6 + b[Q_CLAIMS] * 18, c8);
     }
-    // walk scans (mode 5): the out-rows of every walking pair's current vertex; not counted in
-    // edges_scanned (the traversal's entries), in the scan kernels' time and bytes
+    // walk scans: the out-rows of every walking pair's current vertex
     for (int i = 0; i < nwalk; i++) {
-      const unsigned long long* q = blkq(kWkQ + i);
-      if (!q[Q_EE]) continue;
-      const double wms = dv_ms(evw[size_t(i)][0], evw[size_t(i)][1]);
-      c.timing.expand_ms += wms;
-      c.timing.expand_launches++;
-      c.timing.expand_bytes += q[Q_NCH] * 24 + q[Q_EE] * 5;
-      const unsigned long long c8[8] = {q[Q_NCH], q[Q_EE], 0, fin[D_MEET], (unsigned long long)i, 0, 0, 0};
-      c.timing.hop(5, false, wms, c8);
-      c.timing.name_last_hop("nbg::(anonymous namespace)::k_dv_walk_scan");
+      const unsigned long long* b = blkq(kWkQ + i);
+      if (!b[Q_EE]) continue;
+      const unsigned long long c8[8] = {b[Q_NCH], b[Q_EE], 0, fin[D_MEET], (unsigned long long)i, 0, 0, 0};
+      q.launch_record(5, "nbg::(anonymous namespace)::k_dv_walk_scan", q.event_ms(evw[size_t(i)][0], evw[size_t(i)][1]),
+                      b[Q_EE], b[Q_NCH] * 24 + b[Q_EE] * 5, c8, false);
     }
+  }
+};
 
-    // results (the ends of each path are the host's)
-    const int32_t* hsr = d.h_sr;
-    const int64_t* hoffb = d.h_off;
-    const int64_t plen = hoffb[nb];
-    const size_t base = hpath.size();
-    hpath.resize(base + size_t(plen));
-    if (plen > 0) memcpy(hpath.data() + base, d.h_path, size_t(plen) * 8);
-    for (int64_t p = 0; p < nb; p++) {
-      const int32_t L = hsr[p] == SP_ACTIVE ? -1 : hsr[nb + p];
-      hres[b0 + size_t(p)] = L;
-      if (L >= 0) {
-        hpath[base + size_t(hoffb[p])] = src[b0 + size_t(p)];
-        if (L > 0) hpath[base + size_t(hoffb[p] + L)] = dst[b0 + size_t(p)];
+// rocprim's exclusive scan in its two calls (size query, run): out[i] = in[0] + ... + in[i - 1].
+// Not query_common.h's exclusive_scan_dev: that scans from a `const int64_t*`, another
+// instantiation of rocprim's kernels than the one this file carries, and the header's byte scan
+// would add its kernels to this file's code object.  (Defined after DevBatch: the compiler emits
+// kernel templates in the order the host code first names them.)
+void scan_i64(Ctx& c, int64_t* in, int64_t* out, int64_t n) {
+  size_t tb = 0;
+  NBG_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, int64_t(0), size_t(n), rocprim::plus<int64_t>(), c.stream));
+  c.ws_tmp.ensure(tb);
+  NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, in, out, int64_t(0), size_t(n), rocprim::plus<int64_t>(), c.stream));
+}
+
+// One batch on the host-driven path (k_sp_*): the host sizes every launch from fetched counters,
+// grows the lists and regenerates lost appends.  The overflow fallback, and the whole call with
+// option sp_dev = 0, a sharded owner slice (lo != 0), max_steps > kMaxQ - 2 or B > kPairLds.
+struct HostBatch {
+  PathQuery& q;
+  const size_t b0;
+  const int64_t nb;
+  Ctx& c = q.c;
+  Ctx::SpWork& W = q.W;
+  const int64_t n = q.n, lo = q.lo;
+  unsigned long long* const cnt = W.cnt.as<unsigned long long>();  // the C_* counters (device)
+  unsigned long long* const hc = c.host_counters;                  // their pinned host copy
+  int64_t *const dsv = W.vids.as<int64_t>(), *const dtv = dsv + q.B;  // the pairs' vids and gidx
+  int32_t *const dgs = W.gidx.as<int32_t>(), *const dgt = dgs + q.B;
+
+  // ---- init(), bfs_iteration() ----
+  SpState st{};
+  SpBufs bf{};
+  int64_t n_live[2] = {0, 0}, n_arena = 0, n_meet = 0, active = 0, last_claims = 0;
+  bool arena_lost = false;  // the arena overflowed: reset() wipes every byte instead
+  int32_t iter = 0;
+  // ---- sweep() ----
+  DevBuf swc;  // per pair: pull entries, push entries, the choice
+  unsigned long long *pullc = nullptr, *pushc = nullptr;
+  int32_t* push_pair = nullptr;
+  bool push_ok = false;
+  int64_t n_sw = 0;
+  DevBuf* cur = nullptr;  // the sweep list the step reads; W.sweep[nxt] the one it fills
+  int nxt = 0;
+  // ---- walk(), fetch() ----
+  DevBuf doff, dpath, wk;  // (wk: the walk state, drained by the batch's last fetch)
+  int64_t plen = 0;
+
+  void run() {
+    init();
+    while (active > 0) bfs_iteration();
+    sweep();
+    walk();
+    fetch();
+    reset();
+  }
+
+  // ---- helpers ----
+  void refresh(DevBuf* sweep_next, int64_t cap_sweep_next) {  // bf from the (possibly regrown) lists
+    bf.live_next[0] = W.live_next[0].as<uint64_t>();
+    bf.live_next[1] = W.live_next[1].as<uint64_t>();
+    bf.arena = W.arena.as<uint64_t>();
+    bf.meet = W.meet.as<uint64_t>();
+    bf.cap_live[0] = W.cap_next[0];
+    bf.cap_live[1] = W.cap_next[1];
+    bf.cap_arena = W.cap_arena;
+    bf.cap_meet = W.cap_meet;
+    bf.sweep_next = sweep_next ? sweep_next->as<uint64_t>() : nullptr;
+    bf.cap_sweep = sweep_next ? cap_sweep_next : 0;
+  }
+  // the counters on the host (publish kernel + spin, traverse.hip: a memcpy + stream sync
+  // round trip cost ~20 us per call, ~15 calls per batch)
+  void sync_counters() { fetch_counters(c, cnt, C_N, hc); }
+  void zero(uint32_t mask, int64_t* xdeg = nullptr) { k_cnt_zero<<<1, 64, 0, c.stream>>>(cnt, mask, xdeg); }
+  void set_counter(int which, int64_t v) {
+    hc[32] = (unsigned long long)v;
+    NBG_HIP(hipMemcpyAsync(cnt + which, hc + 32, 8, hipMemcpyHostToDevice, c.stream));
+    NBG_HIP(hipStreamSynchronize(c.stream));
+  }
+  void swap_live() {
+    for (int s = 0; s < 2; s++) {
+      std::swap(W.live[s], W.live_next[s]);
+      std::swap(W.cap_live[s], W.cap_next[s]);
+    }
+  }
+  void ensure_x(int64_t need) {
+    if (need + 1 > W.cap_x) {
+      PoolScope none(nullptr);
+      W.cap_x = std::max<int64_t>(need + need / 4 + 64, 1 << 16);
+      W.X.alloc(size_t(W.cap_x) * 8);
+      W.Xdeg.alloc(size_t(W.cap_x + 1) * 8);
+      W.Xoff.alloc(size_t(W.cap_x + 1) * 8);
+    }
+  }
+  void scan_x(int64_t nX, bool sentinel_zero = false) {  // Xdeg [nX + 1] -> Xoff
+    if (!sentinel_zero) zero(0u, W.Xdeg.as<int64_t>() + nX);
+    scan_i64(c, W.Xdeg.as<int64_t>(), W.Xoff.as<int64_t>(), nX + 1);
+  }
+  void launch_expand(int64_t nX, int64_t E, int32_t sweep) {
+    SpExpand a{};
+    a.X = W.X.as<uint64_t>();
+    a.nX = nX;
+    a.off = W.Xoff.as<int64_t>();
+    a.g[0] = q.gout;
+    a.g[1] = q.gin;
+    a.dist[0] = q.d0;
+    a.dist[1] = q.d1;
+    a.vid_of = q.vid_of;
+    a.n = n;
+    a.lo = lo;
+    a.sweep = sweep;
+    const int64_t tiles = (E + kTileE - 1) / kTileE;
+    const int grid = int(std::max<int64_t>(1, std::min<int64_t>(tiles, 256 * 8)));
+    hipEventRecord(c.ev[2], c.stream);
+    a.tile_row = nullptr;
+    if (nX < (int64_t(1) << 31)) {
+      if (W.tile_rows.bytes < size_t(tiles + 2) * 4) {
+        PoolScope none(nullptr);
+        W.tile_rows.alloc(size_t(tiles + tiles / 4 + 64) * 4);
       }
-      hoff.push_back(hoff.back() + hoffb[p + 1] - hoffb[p]);
+      a.tile_row = W.tile_rows.as<int32_t>();
+      k_tile_rows<kTileE><<<int(std::max<int64_t>(1, std::min<int64_t>((nX + 255) / 256, 4096))), 256, 0, c.stream>>>(
+          a.off, nX, W.tile_rows.as<int32_t>());
     }
-    return true;
-  };
-  c.sp_dirty = true;  // until the batch's bytes are reset
-  for (size_t b0 = 0; b0 < npairs; b0 += size_t(B)) {
-    const int64_t nb = std::min<int64_t>(B, int64_t(npairs - b0));
-    if (dev && run_dev(b0, nb)) {
-      c.timing.spec_hops++;  // nbg_timing.spec_hops of a shortest-path call: batches run device-driven
-      continue;
-    }
-    SpState st{};
+    k_sp_expand<<<grid, kT, 0, c.stream>>>(a, st, bf, cnt);
+    NBG_HIP(hipGetLastError());
+    hipEventRecord(c.ev[3], c.stream);
+  }
+  double ev_ms(int a, int b) const {
+    float ms = 0;
+    hipEventElapsedTime(&ms, c.ev[a], c.ev[b]);
+    return ms;
+  }
+  // a launch record with c8 = {X tuples, adjacency entries, claims, meets (total so far),
+  // iteration, active pairs, 0, 0}
+  void record(int32_t mode, double ms, int64_t nX, int64_t E, int64_t claims, int64_t it, int64_t act, uint64_t bytes) {
+    const unsigned long long c8[8] = {(unsigned long long)nX, (unsigned long long)E, (unsigned long long)claims,
+                                      hc[C_MEET], (unsigned long long)it, (unsigned long long)act, 0, 0};
+    q.launch_record(mode,
+                    mode == 3                      ? "nbg::(anonymous namespace)::k_sp_probe"
+                    : mode == 4 && q.sweep_chunks ? "nbg::(anonymous namespace)::k_sp_sweep"
+                                                  : "nbg::(anonymous namespace)::k_sp_expand",
+                    ms, uint64_t(E), bytes, c8);
+  }
+  // pairs (of this batch) matching a host predicate over (state, pside, met) -> W.plist
+  template <typename Pred>
+  int32_t pair_list(Pred pred) {
+    NBG_HIP(hipMemcpyAsync(q.hstate.data(), st.state, size_t(nb) * 4, hipMemcpyDeviceToHost, c.stream));
+    NBG_HIP(hipMemcpyAsync(q.hside.data(), st.pside, size_t(nb) * 4, hipMemcpyDeviceToHost, c.stream));
+    NBG_HIP(hipMemcpyAsync(q.hmet.data(), st.met, size_t(nb) * 4, hipMemcpyDeviceToHost, c.stream));
+    NBG_HIP(hipStreamSynchronize(c.stream));
+    std::vector<int32_t> pl;
+    for (int32_t p = 0; p < int32_t(nb); p++)
+      if (pred(q.hstate[size_t(p)], q.hside[size_t(p)], q.hmet[size_t(p)])) pl.push_back(p);
+    if (!pl.empty()) NBG_HIP(hipMemcpy(W.plist.p, pl.data(), pl.size() * 4, hipMemcpyHostToDevice));
+    return int32_t(pl.size());
+  }
+  // the appends a list lost to an overflow, again from the distance bytes of the listed pairs
+  void regen(int mode, int side, int32_t j, int32_t np, uint64_t* outl, int64_t cap, int which) {
+    if (np == 0) return;
+    dim3 grid(unsigned(std::min<int64_t>((n + 255) / 256, 1024)), unsigned(std::min<int32_t>(np, 65535)));
+    k_sp_regen<<<grid, 256, 0, c.stream>>>(mode, side, j, W.plist.as<int32_t>(), np, st, q.d0, q.d1, n, outl, cap, cnt,
+                                           which);
+    NBG_HIP(hipGetLastError());
+  }
+
+  // ---- phases ----
+  // per-pair state, the level bitmaps, the pairs' gidx, depth 0 of both sides
+  void init() {
     st.B = int32_t(nb);
     sp_state_carve(W.state, nb, st);
-    st.ilv = ilv;
-    if (c.opt("sp_lvbits", 1) != 0) {  // level filter: 2 * kLv maps, cleared per batch
-      // bits per level: the power of two >= n, capped (option sp_lvbits_log2, default 23)
-      const int cap = int(std::min<int64_t>(std::max<int64_t>(23, 5), 31));
+    st.ilv = q.ilv;
+    if (q.lvbits_on) {  // level filter: 2 * kLv maps, cleared per batch
+      // bits per level: the power of two >= n, at most 2^kLvBitsLog2Max
       int lg = 5;
-      while (lg < cap && (int64_t(1) << lg) < n) lg++;
+      while (lg < kLvBitsLog2Max && (int64_t(1) << lg) < n) lg++;
       const int64_t lvw = (int64_t(1) << lg) / 32;
       st.lvmask = uint32_t((uint64_t(1) << lg) - 1);
       const size_t lvb = size_t(2 * kLv) * size_t(lvw) * 4;
@@ -3214,414 +3535,273 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
       st.lvbits = W.lvbits.as<uint32_t>();
       st.lvw = lvw;
     }
+    const int64_t* src = q.src + b0;
+    const int64_t* dst = q.dst + b0;
     if (c.host_stage && c.host_stage_used == 0 && size_t(nb) * 16 <= kHostStageBytes) {
       // through the pinned stage: a pageable source makes the copy wait on the host (the stage's
       // previous contents, the last batch's results, were read back before this point)
       int64_t* hs = static_cast<int64_t*>(c.host_stage);
-      memcpy(hs, src + b0, size_t(nb) * 8);
-      memcpy(hs + nb, dst + b0, size_t(nb) * 8);
-      NBG_HIP(hipMemcpyAsync(dsv, hs, size_t(nb) * 8, hipMemcpyHostToDevice, c.stream));
-      NBG_HIP(hipMemcpyAsync(dtv, hs + nb, size_t(nb) * 8, hipMemcpyHostToDevice, c.stream));
-    } else {
-      NBG_HIP(hipMemcpyAsync(dsv, src + b0, size_t(nb) * 8, hipMemcpyHostToDevice, c.stream));
-      NBG_HIP(hipMemcpyAsync(dtv, dst + b0, size_t(nb) * 8, hipMemcpyHostToDevice, c.stream));
+      memcpy(hs, src, size_t(nb) * 8);
+      memcpy(hs + nb, dst, size_t(nb) * 8);
+      src = hs;
+      dst = hs + nb;
     }
+    NBG_HIP(hipMemcpyAsync(dsv, src, size_t(nb) * 8, hipMemcpyHostToDevice, c.stream));
+    NBG_HIP(hipMemcpyAsync(dtv, dst, size_t(nb) * 8, hipMemcpyHostToDevice, c.stream));
     lookup_gidx(c, dsv, dgs, nb);
     lookup_gidx(c, dtv, dgt, nb);
     NBG_HIP(hipMemsetAsync(cnt, 0, C_N * 8, c.stream));
     for (int s = 0; s < 2; s++) reserve(c, W.live_next[s], W.cap_next[s], nb + 64, 0);
     reserve(c, W.arena, W.cap_arena, 2 * nb + 64, 0);
     reserve(c, W.meet, W.cap_meet, 4096, 0);
-    SpBufs bf{};
-    auto refresh = [&](DevBuf* sweep_next, int64_t cap_sweep_next) {
-      bf.live_next[0] = W.live_next[0].as<uint64_t>();
-      bf.live_next[1] = W.live_next[1].as<uint64_t>();
-      bf.arena = W.arena.as<uint64_t>();
-      bf.meet = W.meet.as<uint64_t>();
-      bf.cap_live[0] = W.cap_next[0];
-      bf.cap_live[1] = W.cap_next[1];
-      bf.cap_arena = W.cap_arena;
-      bf.cap_meet = W.cap_meet;
-      bf.sweep_next = sweep_next ? sweep_next->as<uint64_t>() : nullptr;
-      bf.cap_sweep = sweep_next ? cap_sweep_next : 0;
-    };
-    // the counters on the host (publish kernel + spin, traverse.hip: a memcpy + stream sync
-    // round trip cost ~20 us per call, ~15 calls per batch)
-    auto sync_counters = [&]() { fetch_counters(c, cnt, C_N, hc); };
-    auto zero = [&](uint32_t mask, int64_t* xdeg = nullptr) {
-      k_cnt_zero<<<1, 64, 0, c.stream>>>(cnt, mask, xdeg);
-    };
-    auto set_counter = [&](int which, int64_t v) {
-      hc[32] = (unsigned long long)v;
-      NBG_HIP(hipMemcpyAsync(cnt + which, hc + 32, 8, hipMemcpyHostToDevice, c.stream));
-      NBG_HIP(hipStreamSynchronize(c.stream));
-    };
-    auto ensure_x = [&](int64_t need) {
-      if (need + 1 > W.cap_x) {
-        PoolScope none(nullptr);
-        W.cap_x = std::max<int64_t>(need + need / 4 + 64, 1 << 16);
-        W.X.alloc(size_t(W.cap_x) * 8);
-        W.Xdeg.alloc(size_t(W.cap_x + 1) * 8);
-        W.Xoff.alloc(size_t(W.cap_x + 1) * 8);
-      }
-    };
-    auto launch_scan = [&](int64_t nX, bool sentinel_zero = false) {
-      size_t tb = 0;
-      if (!sentinel_zero) zero(0u, W.Xdeg.as<int64_t>() + nX);
-      NBG_HIP(rocprim::exclusive_scan(nullptr, tb, W.Xdeg.as<int64_t>(), W.Xoff.as<int64_t>(), int64_t(0),
-                                      size_t(nX + 1), rocprim::plus<int64_t>(), c.stream));
-      c.ws_tmp.ensure(tb);
-      NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, W.Xdeg.as<int64_t>(), W.Xoff.as<int64_t>(), int64_t(0),
-                                      size_t(nX + 1), rocprim::plus<int64_t>(), c.stream));
-    };
-    auto launch_expand = [&](int64_t nX, int64_t E, int32_t sweep_mode) {
-      SpExpand a{};
-      a.X = W.X.as<uint64_t>();
-      a.nX = nX;
-      a.off = W.Xoff.as<int64_t>();
-      a.g[0] = gout;
-      a.g[1] = gin;
-      a.dist[0] = d0;
-      a.dist[1] = d1;
-      a.vid_of = vid_of;
-      a.n = n;
-      a.lo = lo;
-      a.sweep = sweep_mode;
-      const int64_t tiles = (E + kTileE - 1) / kTileE;
-      const int grid = int(std::max<int64_t>(1, std::min<int64_t>(tiles, 256 * 8)));
-      hipEventRecord(c.ev[2], c.stream);
-      a.tile_row = nullptr;
-      if (nX < (int64_t(1) << 31)) {
-        if (W.tile_rows.bytes < size_t(tiles + 2) * 4) {
-          PoolScope none(nullptr);
-          W.tile_rows.alloc(size_t(tiles + tiles / 4 + 64) * 4);
-        }
-        a.tile_row = W.tile_rows.as<int32_t>();
-        k_tile_rows<kTileE><<<int(std::max<int64_t>(1, std::min<int64_t>((nX + 255) / 256, 4096))), 256, 0, c.stream>>>(
-            a.off, nX, W.tile_rows.as<int32_t>());
-      }
-      k_sp_expand<<<grid, kT, 0, c.stream>>>(a, st, bf, cnt);
-      NBG_HIP(hipGetLastError());
-      hipEventRecord(c.ev[3], c.stream);
-    };
-    auto expand_time = [&]() -> double {
-      float ms = 0;
-      hipEventElapsedTime(&ms, c.ev[2], c.ev[3]);
-      c.timing.expand_ms += ms;
-      c.timing.expand_launches++;
-      return ms;
-    };
-    // per-launch record in the hop stats: mode 2 = BFS expansion, 3 = meet probe, 4 = sweep;
-    // c[] = {X tuples, adjacency entries, claims, meets (total so far), iteration, active pairs}
-    unsigned long long diag[2] = {0, 0};  // (c[6], c[7] of the sweep records: unused since round 6)
-    auto sp_hop = [&](int32_t mode, double ms, int64_t nX, int64_t E, int64_t claims, int64_t it, int64_t act) {
-      const unsigned long long c8[8] = {(unsigned long long)nX, (unsigned long long)E, (unsigned long long)claims,
-                                        hc[C_MEET], (unsigned long long)it, (unsigned long long)act, diag[0], diag[1]};
-      diag[0] = diag[1] = 0;
-      c.timing.hop(mode, false, ms, c8);
-      c.timing.name_last_hop(mode == 3   ? "nbg::(anonymous namespace)::k_sp_probe"
-                             : mode == 4 && c.opt("sp_sweep_chunks", 1) != 0 ? "nbg::(anonymous namespace)::k_sp_sweep"
-                                                                             : "nbg::(anonymous namespace)::k_sp_expand");
-    };
-    // pairs (of this batch) matching a host predicate over (state, pside, met) -> W.plist
-    auto pair_list = [&](auto pred) -> int32_t {
-      NBG_HIP(hipMemcpyAsync(hstate.data(), st.state, size_t(nb) * 4, hipMemcpyDeviceToHost, c.stream));
-      NBG_HIP(hipMemcpyAsync(hside.data(), st.pside, size_t(nb) * 4, hipMemcpyDeviceToHost, c.stream));
-      NBG_HIP(hipMemcpyAsync(hmet.data(), st.met, size_t(nb) * 4, hipMemcpyDeviceToHost, c.stream));
-      NBG_HIP(hipStreamSynchronize(c.stream));
-      std::vector<int32_t> pl;
-      for (int32_t p = 0; p < int32_t(nb); p++)
-        if (pred(hstate[size_t(p)], hside[size_t(p)], hmet[size_t(p)])) pl.push_back(p);
-      if (!pl.empty())
-        NBG_HIP(hipMemcpy(W.plist.p, pl.data(), pl.size() * 4, hipMemcpyHostToDevice));
-      return int32_t(pl.size());
-    };
-    auto regen = [&](int mode, int side, int32_t j, int32_t np, uint64_t* outl, int64_t cap, int which) {
-      if (np == 0) return;
-      dim3 grid(unsigned(std::min<int64_t>((n + 255) / 256, 1024)), unsigned(std::min<int32_t>(np, 65535)));
-      k_sp_regen<<<grid, 256, 0, c.stream>>>(mode, side, j, W.plist.as<int32_t>(), np, st, d0, d1, n, outl, cap, cnt,
-                                             which);
-      NBG_HIP(hipGetLastError());
-    };
-
-    k_sp_init<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(dsv, dtv, dgs, dgt, int32_t(nb), max_steps, n, st, gout, gin,
-                                                         d0, d1, (refresh(nullptr, 0), bf), cnt);
-    k_sp_step<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(st, max_steps, 1, 0, cnt);
+    refresh(nullptr, 0);
+    k_sp_init<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(dsv, dtv, dgs, dgt, int32_t(nb), q.max_steps, n, st,
+                                                         q.gout, q.gin, q.d0, q.d1, bf, cnt);
+    k_sp_step<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(st, q.max_steps, 1, 0, cnt);
     NBG_HIP(hipGetLastError());
     sync_counters();
-    int64_t n_live[2] = {int64_t(hc[C_LIVE0]), int64_t(hc[C_LIVE1])};
-    int64_t n_arena = int64_t(hc[C_ARENA]), n_meet = 0;
-    int64_t active = int64_t(hc[C_ACTIVE]);
-    int64_t last_claims = 0;
-    bool arena_lost = false;
-    for (int s = 0; s < 2; s++) {
-      std::swap(W.live[s], W.live_next[s]);
-      std::swap(W.cap_live[s], W.cap_next[s]);
-    }
-    int32_t iter = 0;
-    while (active > 0) {
-      iter++;
-      c.timing.steps_run++;
-      // live lists -> X (expanding side) + carried tuples
-      ensure_x(n_live[0] + n_live[1]);
-      for (int s = 0; s < 2; s++) reserve(c, W.live_next[s], W.cap_next[s], n_live[s] + 64, 0);
-      refresh(nullptr, 0);
-      zero(1u << C_LIVE0 | 1u << C_LIVE1 | 1u << C_X | 1u << C_ACTIVE | 1u << C_OVF | 1u << C_XE);
-      for (int s = 0; s < 2; s++)
-        if (n_live[s])
-          k_sp_select<<<grid_sel(n_live[s]), kBlk, 0, c.stream>>>(W.live[s].as<uint64_t>(), n_live[s], 0, st, gout, gin,
-                                                                 W.X.as<uint64_t>(), W.Xdeg.as<int64_t>(), W.cap_x, bf,
-                                                                 cnt);
-      NBG_HIP(hipGetLastError());
-      sync_counters();
-      if (hc[C_OVF] & 2) throw Error(NBG_E_UNKNOWN, "shortest path: frontier list overflow");
-      const int64_t nX = int64_t(hc[C_X]);
-      int64_t E = int64_t(hc[C_XE]);
-      const int64_t carried[2] = {int64_t(hc[C_LIVE0]), int64_t(hc[C_LIVE1])};
-      // The probe's results (meets, claims, the dropped pairs' degrees) are read with the
-      // iteration's last counter fetch: the expansion is sized by the pre-probe E (an upper
-      // bound; it reads its own E from the scan on the device) and the lists keep room for
-      // every probe claim, so no round trip separates the probe from the expansion.
-      DevBuf ch, choff, slot, chx;  // live until the fetch below (stream-ordered reuse aside)
-      int64_t max_chunks = 0;
-      const bool probed = E > 0 && probe;
-      if (probed) {
-        // meet probe: pairs one edge short of meeting skip this iteration's expansion
-        max_chunks = nX + E / kProbeCh + 64;
-        reserve(c, W.meet, W.cap_meet, n_meet + max_chunks, n_meet);
-        if (!arena_lost) reserve(c, W.arena, W.cap_arena, n_arena + max_chunks, n_arena);
-        refresh(nullptr, 0);
-        ch.alloc(size_t(nX + 1) * 8);
-        choff.alloc(size_t(nX + 1) * 8);
-        slot.alloc(size_t(max_chunks) * 8);
-        k_sp_chunks<<<grid_n(nX + 1), 256, 0, c.stream>>>(W.Xdeg.as<int64_t>(), nX, ch.as<int64_t>(), cnt);
-        size_t tb = 0;
-        NBG_HIP(rocprim::exclusive_scan(nullptr, tb, ch.as<int64_t>(), choff.as<int64_t>(), int64_t(0),
-                                        size_t(nX + 1), rocprim::plus<int64_t>(), c.stream));
-        c.ws_tmp.ensure(tb);
-        NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, ch.as<int64_t>(), choff.as<int64_t>(), int64_t(0),
-                                        size_t(nX + 1), rocprim::plus<int64_t>(), c.stream));
-        hipEventRecord(c.ev[4], c.stream);
-        const int pgrid =
-            int(std::max<int64_t>(1, std::min<int64_t>((max_chunks + 3) / 4, 4096)));
-        chx.alloc(size_t(max_chunks) * 4);
-        k_chunk_x<<<grid_n(nX), 256, 0, c.stream>>>(choff.as<int64_t>(), nX, chx.as<int32_t>(), slot.as<uint64_t>());
-        k_sp_probe<1><<<pgrid, 256, 0, c.stream>>>(W.X.as<uint64_t>(), nX, choff.as<int64_t>(), chx.as<int32_t>(),
-                                                     gout, gin, d0, d1, n, lo, st, slot.as<uint64_t>(), cnt);
-        k_sp_gather_meets<<<grid_sel(max_chunks), kBlk, 0, c.stream>>>(slot.as<uint64_t>(), max_chunks, st, bf, cnt,
-                                                                       choff.as<int64_t>() + nX);
-        k_sp_probe_end<<<grid_n(std::max<int64_t>(nb, nX)), 256, 0, c.stream>>>(st, iter, W.X.as<uint64_t>(),
-                                                                                W.Xdeg.as<int64_t>(), nX, cnt);
-        NBG_HIP(hipGetLastError());
-        hipEventRecord(c.ev[5], c.stream);
-      }
-      // the probe's meets and claims are at most one per chunk
-      const int64_t meet_keep = n_meet + max_chunks, arena_keep = n_arena + max_chunks;
-      if (E > 0) {
-        // lists sized for min(every edge claims, a soft bound); an overflow is rebuilt below
-        const int64_t want = std::min<int64_t>(E, std::max<int64_t>(soft, 2 * last_claims)) + 64;
-        for (int s = 0; s < 2; s++) reserve(c, W.live_next[s], W.cap_next[s], carried[s] + want, carried[s]);
-        if (!arena_lost)
-          reserve(c, W.arena, W.cap_arena, arena_keep + want, std::min<int64_t>(arena_keep, W.cap_arena));
-        reserve(c, W.meet, W.cap_meet, meet_keep + std::min<int64_t>(E, soft) + 64, std::min<int64_t>(meet_keep, W.cap_meet));
-        refresh(nullptr, 0);
-        launch_scan(nX, probed);  // (k_sp_probe_end cleared the sentinel)
-        launch_expand(nX, E, 0);
-      }
-      k_sp_step<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(st, max_steps, 0, iter, cnt);
-      NBG_HIP(hipGetLastError());
-      sync_counters();
-      if (probed) {
-        float pms = 0;
-        hipEventElapsedTime(&pms, c.ev[4], c.ev[5]);
-        c.timing.expand_ms += pms;
-        c.timing.expand_launches++;
-        c.timing.edges_scanned += hc[C_PE];
-        c.timing.expand_bytes += uint64_t(nX) * 24 + hc[C_PE] * 5;
-        sp_hop(3, pms, nX, int64_t(hc[C_PE]), 0, iter, active);
-      }
-      const bool launched = E > 0;
-      E = int64_t(hc[C_XE]);  // after the probe's drops: the expansion's own E
-      c.timing.edges_scanned += uint64_t(E);
-      const double ems = launched && E > 0 ? expand_time() : 0.0;
-      const int64_t cl = int64_t(hc[C_LIVE0] + hc[C_LIVE1]) - carried[0] - carried[1];
-      last_claims = cl;
-      c.timing.expand_bytes += uint64_t(nX) * 32 + uint64_t(E) * 5 + uint64_t(cl) * 26;
-      if (E > 0) sp_hop(2, ems, nX, E, cl, iter, active);
-      if (int64_t(hc[C_ARENA]) > W.cap_arena) arena_lost = true;  // the batch end resets every byte instead
-      n_arena = std::min<int64_t>(int64_t(hc[C_ARENA]), W.cap_arena);
-      bool regen_done = false;
-      for (int s = 0; s < 2; s++) {
-        if (int64_t(hc[C_LIVE0 + s]) <= W.cap_next[s]) continue;
-        regen_done = true;
-        const int64_t total = int64_t(hc[C_LIVE0 + s]);
-        reserve(c, W.live_next[s], W.cap_next[s], total + 64, carried[s]);
-        const int32_t np = pair_list([s](int32_t stt, int32_t ps, int32_t) { return stt == SP_ACTIVE && ps == s; });
-        set_counter(C_LIVE0 + s, carried[s]);
-        regen(RG_LIVE, s, 0, np, W.live_next[s].as<uint64_t>(), W.cap_next[s], C_LIVE0 + s);
-      }
-      if (int64_t(hc[C_MEET]) > W.cap_meet) {
-        regen_done = true;
-        reserve(c, W.meet, W.cap_meet, int64_t(hc[C_MEET]) + 64, n_meet);
-        const int32_t tag = 2 + iter;
-        const int32_t np = pair_list([tag](int32_t stt, int32_t, int32_t m) { return stt == SP_MET && m == tag; });
-        set_counter(C_MEET, n_meet);
-        regen(RG_MEET, 1, 0, np, W.meet.as<uint64_t>(), W.cap_meet, C_MEET);
-      }
-      if (regen_done) sync_counters();  // the regenerated lists' counts
-      n_live[0] = int64_t(hc[C_LIVE0]);
-      n_live[1] = int64_t(hc[C_LIVE1]);
-      n_meet = int64_t(hc[C_MEET]);
-      active = int64_t(hc[C_ACTIVE]);
-      for (int s = 0; s < 2; s++) {
-        std::swap(W.live[s], W.live_next[s]);
-        std::swap(W.cap_live[s], W.cap_next[s]);
-      }
-    }
+    n_live[0] = int64_t(hc[C_LIVE0]);
+    n_live[1] = int64_t(hc[C_LIVE1]);
+    n_arena = int64_t(hc[C_ARENA]);
+    active = int64_t(hc[C_ACTIVE]);
+    swap_live();
+  }
 
-    // sweep: extend dist_B from the meet sets toward src along shortest paths only
-    int64_t n_sw = n_meet;
-    const int32_t sweep_mode = c.opt("sp_sweep_src", 0) ? 1 : 2;
-    DevBuf* cur = &W.meet;
-    int nxt = 0;
+  // select, meet probe, expansion, step; lists that overflowed are regenerated
+  void bfs_iteration() {
+    iter++;
+    c.timing.steps_run++;
+    // live lists -> X (expanding side) + carried tuples
+    ensure_x(n_live[0] + n_live[1]);
+    for (int s = 0; s < 2; s++) reserve(c, W.live_next[s], W.cap_next[s], n_live[s] + 64, 0);
+    refresh(nullptr, 0);
+    zero(1u << C_LIVE0 | 1u << C_LIVE1 | 1u << C_X | 1u << C_ACTIVE | 1u << C_OVF | 1u << C_XE);
+    for (int s = 0; s < 2; s++)
+      if (n_live[s])
+        k_sp_select<<<grid_sel(n_live[s]), kBlk, 0, c.stream>>>(W.live[s].as<uint64_t>(), n_live[s], 0, st, q.gout, q.gin,
+                                                               W.X.as<uint64_t>(), W.Xdeg.as<int64_t>(), W.cap_x, bf, cnt);
+    NBG_HIP(hipGetLastError());
+    sync_counters();
+    if (hc[C_OVF] & 2) throw Error(NBG_E_UNKNOWN, "shortest path: frontier list overflow");
+    const int64_t nX = int64_t(hc[C_X]);
+    int64_t E = int64_t(hc[C_XE]);
+    const int64_t carried[2] = {int64_t(hc[C_LIVE0]), int64_t(hc[C_LIVE1])};
+    // The probe's results (meets, claims, the dropped pairs' degrees) are read with the
+    // iteration's last counter fetch: the expansion is sized by the pre-probe E (an upper
+    // bound; it reads its own E from the scan on the device) and the lists keep room for
+    // every probe claim, so no round trip separates the probe from the expansion.
+    DevBuf ch, choff, slot, chx;  // live until the fetch below (stream-ordered reuse aside)
+    int64_t max_chunks = 0;
+    const bool probed = E > 0 && q.probe;
+    if (probed) {
+      // meet probe: pairs one edge short of meeting skip this iteration's expansion
+      max_chunks = nX + E / kProbeCh + 64;
+      reserve(c, W.meet, W.cap_meet, n_meet + max_chunks, n_meet);
+      if (!arena_lost) reserve(c, W.arena, W.cap_arena, n_arena + max_chunks, n_arena);
+      refresh(nullptr, 0);
+      ch.alloc(size_t(nX + 1) * 8);
+      choff.alloc(size_t(nX + 1) * 8);
+      slot.alloc(size_t(max_chunks) * 8);
+      k_sp_chunks<<<grid_n(nX + 1), 256, 0, c.stream>>>(W.Xdeg.as<int64_t>(), nX, ch.as<int64_t>(), cnt);
+      scan_i64(c, ch.as<int64_t>(), choff.as<int64_t>(), nX + 1);
+      hipEventRecord(c.ev[4], c.stream);
+      const int pgrid = int(std::max<int64_t>(1, std::min<int64_t>((max_chunks + 3) / 4, 4096)));
+      chx.alloc(size_t(max_chunks) * 4);
+      k_chunk_x<<<grid_n(nX), 256, 0, c.stream>>>(choff.as<int64_t>(), nX, chx.as<int32_t>(), slot.as<uint64_t>());
+      k_sp_probe<1><<<pgrid, 256, 0, c.stream>>>(W.X.as<uint64_t>(), nX, choff.as<int64_t>(), chx.as<int32_t>(), q.gout,
+                                                 q.gin, q.d0, q.d1, n, lo, st, slot.as<uint64_t>(), cnt);
+      k_sp_gather_meets<<<grid_sel(max_chunks), kBlk, 0, c.stream>>>(slot.as<uint64_t>(), max_chunks, st, bf, cnt,
+                                                                     choff.as<int64_t>() + nX);
+      k_sp_probe_end<<<grid_n(std::max<int64_t>(nb, nX)), 256, 0, c.stream>>>(st, iter, W.X.as<uint64_t>(),
+                                                                              W.Xdeg.as<int64_t>(), nX, cnt);
+      NBG_HIP(hipGetLastError());
+      hipEventRecord(c.ev[5], c.stream);
+    }
+    // the probe's meets and claims are at most one per chunk
+    const int64_t meet_keep = n_meet + max_chunks, arena_keep = n_arena + max_chunks;
+    if (E > 0) {
+      // lists sized for min(every edge claims, a soft bound); an overflow is rebuilt below
+      const int64_t want = std::min<int64_t>(E, std::max<int64_t>(q.soft, 2 * last_claims)) + 64;
+      for (int s = 0; s < 2; s++) reserve(c, W.live_next[s], W.cap_next[s], carried[s] + want, carried[s]);
+      if (!arena_lost)
+        reserve(c, W.arena, W.cap_arena, arena_keep + want, std::min<int64_t>(arena_keep, W.cap_arena));
+      reserve(c, W.meet, W.cap_meet, meet_keep + std::min<int64_t>(E, q.soft) + 64, std::min<int64_t>(meet_keep, W.cap_meet));
+      refresh(nullptr, 0);
+      scan_x(nX, probed);  // (k_sp_probe_end cleared the sentinel)
+      launch_expand(nX, E, 0);
+    }
+    k_sp_step<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(st, q.max_steps, 0, iter, cnt);
+    NBG_HIP(hipGetLastError());
+    sync_counters();
+    if (probed)
+      record(3, ev_ms(4, 5), nX, int64_t(hc[C_PE]), 0, iter, active, uint64_t(nX) * 24 + hc[C_PE] * 5);
+    E = int64_t(hc[C_XE]);  // after the probe's drops: the expansion's own E (0 when none was launched)
+    const int64_t cl = int64_t(hc[C_LIVE0] + hc[C_LIVE1]) - carried[0] - carried[1];
+    last_claims = cl;
+    const uint64_t ebytes = uint64_t(nX) * 32 + uint64_t(E) * 5 + uint64_t(cl) * 26;
+    if (E > 0) record(2, ev_ms(2, 3), nX, E, cl, iter, active, ebytes);
+    else c.timing.expand_bytes += ebytes;  // (no record: the bytes count toward the next one)
+    if (int64_t(hc[C_ARENA]) > W.cap_arena) arena_lost = true;
+    n_arena = std::min<int64_t>(int64_t(hc[C_ARENA]), W.cap_arena);
+    bool regen_done = false;
+    for (int s = 0; s < 2; s++) {
+      if (int64_t(hc[C_LIVE0 + s]) <= W.cap_next[s]) continue;
+      regen_done = true;
+      const int64_t total = int64_t(hc[C_LIVE0 + s]);
+      reserve(c, W.live_next[s], W.cap_next[s], total + 64, carried[s]);
+      const int32_t np = pair_list([s](int32_t stt, int32_t ps, int32_t) { return stt == SP_ACTIVE && ps == s; });
+      set_counter(C_LIVE0 + s, carried[s]);
+      regen(RG_LIVE, s, 0, np, W.live_next[s].as<uint64_t>(), W.cap_next[s], C_LIVE0 + s);
+    }
+    if (int64_t(hc[C_MEET]) > W.cap_meet) {
+      regen_done = true;
+      reserve(c, W.meet, W.cap_meet, int64_t(hc[C_MEET]) + 64, n_meet);
+      const int32_t tag = 2 + iter;
+      const int32_t np = pair_list([tag](int32_t stt, int32_t, int32_t m) { return stt == SP_MET && m == tag; });
+      set_counter(C_MEET, n_meet);
+      regen(RG_MEET, 1, 0, np, W.meet.as<uint64_t>(), W.cap_meet, C_MEET);
+    }
+    if (regen_done) sync_counters();  // the regenerated lists' counts
+    n_live[0] = int64_t(hc[C_LIVE0]);
+    n_live[1] = int64_t(hc[C_LIVE1]);
+    n_meet = int64_t(hc[C_MEET]);
+    active = int64_t(hc[C_ACTIVE]);
+    swap_live();
+  }
+
+  // extend dist_B from the meet sets toward src along shortest paths only
+  void sweep() {
+    n_sw = n_meet;
+    cur = &W.meet;
     // per pair and step: pull (in-rows of the level above) or push (out-rows of the forward
     // level, from the arena) -- needs every forward claim in the arena
-    const bool push_ok = c.opt("sp_sweep_push", 1) != 0 && !arena_lost && sweep_mode == 2;
-    DevBuf swc;
-    unsigned long long *pullc = nullptr, *pushc = nullptr;
-    int32_t* push_pair = nullptr;
+    push_ok = q.sweep_push && !arena_lost && q.sweep_mode == 2;
     if (push_ok) {
       swc.alloc(size_t(nb) * 20 + 64);
       pullc = swc.as<unsigned long long>();
       pushc = pullc + nb;
       push_pair = reinterpret_cast<int32_t*>(pushc + nb);
     }
-    for (int32_t j = 1; n_sw > 0; j++) {
-      const bool push_now = push_ok && !arena_lost;  // an arena overflow mid-sweep: pull only
-      ensure_x(n_sw + (push_now ? n_arena : 0));
-      k_cnt_zero<<<1, 256, 0, c.stream>>>(cnt, 1u << C_X | 1u << C_ACTIVE | 1u << C_OVF | 1u << C_SWEEP | 1u << C_XE,
-                                          nullptr, push_now ? pullc : nullptr, push_now ? 2 * nb : 0);
-      refresh(nullptr, 0);
-      if (push_now) {
-        k_sweep_pull_cost<<<grid_n(n_sw), 256, 0, c.stream>>>(cur->as<uint64_t>(), n_sw, sweep_mode, st, gin, pullc);
-        if (n_arena)
-          k_sweep_push_cost<<<grid_n(n_arena), 256, 0, c.stream>>>(W.arena.as<uint64_t>(), n_arena, j, st, gout, pullc,
-                                                                    pushc);
-        k_sweep_choose<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(
-            pullc, pushc, int32_t(nb), push_pair, (unsigned long long)std::max<int64_t>(0, 16));
-      }
-      k_sp_select<<<grid_sel(n_sw), kBlk, 0, c.stream>>>(cur->as<uint64_t>(), n_sw, sweep_mode, st, gout, gin, W.X.as<uint64_t>(),
-                                                       W.Xdeg.as<int64_t>(), W.cap_x, bf, cnt,
-                                                       push_now ? push_pair : nullptr);
-      if (push_now && n_arena)
-        k_sweep_push_select<<<grid_n(n_arena), 256, 0, c.stream>>>(W.arena.as<uint64_t>(), n_arena, j, st, gout,
-                                                                    push_pair, W.X.as<uint64_t>(),
-                                                                    W.Xdeg.as<int64_t>(), W.cap_x, cnt);
-      NBG_HIP(hipGetLastError());
-      sync_counters();
-      const int64_t nX = int64_t(hc[C_X]), E = int64_t(hc[C_XE]);
-      if (nX == 0 || E == 0) break;
-      c.timing.edges_scanned += uint64_t(E);
-      const int64_t want = std::min<int64_t>(E, soft) + 64;
-      reserve(c, W.sweep[nxt], W.cap_sweep[nxt], want, 0);
-      if (!arena_lost) reserve(c, W.arena, W.cap_arena, n_arena + want, n_arena);
-      refresh(&W.sweep[nxt], W.cap_sweep[nxt]);
-      if (c.opt("sp_sweep_chunks", 1) != 0) {
-        // chunk counts -> their scan -> chunk table -> one wave per chunk
-        DevBuf ch, choff, chx;
-        ch.alloc(size_t(nX + 1) * 8);
-        choff.alloc(size_t(nX + 1) * 8);
-        k_sp_chunks_n<<<grid_n(nX + 1), 256, 0, c.stream>>>(W.Xdeg.as<int64_t>(), nX, ch.as<int64_t>(), kSwCh);
-        size_t tb = 0;
-        NBG_HIP(rocprim::exclusive_scan(nullptr, tb, ch.as<int64_t>(), choff.as<int64_t>(), int64_t(0),
-                                        size_t(nX + 1), rocprim::plus<int64_t>(), c.stream));
-        c.ws_tmp.ensure(tb);
-        NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, ch.as<int64_t>(), choff.as<int64_t>(), int64_t(0),
-                                        size_t(nX + 1), rocprim::plus<int64_t>(), c.stream));
-        const int64_t max_ch = nX + E / kSwCh + 1;
-        chx.alloc(size_t(max_ch) * 4);
-        hipEventRecord(c.ev[2], c.stream);
-        k_chunk_x<<<grid_n(nX), 256, 0, c.stream>>>(choff.as<int64_t>(), nX, chx.as<int32_t>());
-        const int sgrid = int(std::max<int64_t>(1, std::min<int64_t>((max_ch + 3) / 4, 8192)));
-        k_sp_sweep<1><<<sgrid, 256, 0, c.stream>>>(W.X.as<uint64_t>(), choff.as<int64_t>(), chx.as<int32_t>(), nX,
-                                                      gout, gin, d0, d1, n, lo, st, bf, cnt);
-        NBG_HIP(hipGetLastError());
-        hipEventRecord(c.ev[3], c.stream);
-      } else {
-        launch_scan(nX);
-        launch_expand(nX, E, 1);
-      }
-      sync_counters();
-      const double sms = expand_time();
-      c.timing.expand_bytes += uint64_t(nX) * 32 + uint64_t(E) * 6 + hc[C_SWEEP] * 18;
-      sp_hop(4, sms, nX, E, int64_t(hc[C_SWEEP]), j, 0);
-      if (int64_t(hc[C_ARENA]) > W.cap_arena) arena_lost = true;
-      n_arena = std::min<int64_t>(int64_t(hc[C_ARENA]), W.cap_arena);
-      if (int64_t(hc[C_SWEEP]) > W.cap_sweep[nxt]) {
-        reserve(c, W.sweep[nxt], W.cap_sweep[nxt], int64_t(hc[C_SWEEP]) + 64, 0);
-        const int32_t np = pair_list([](int32_t stt, int32_t, int32_t) { return stt == SP_MET; });
-        set_counter(C_SWEEP, 0);
-        regen(RG_SWEEP, 1, j, np, W.sweep[nxt].as<uint64_t>(), W.cap_sweep[nxt], C_SWEEP);
-        sync_counters();
-      }
-      n_sw = int64_t(hc[C_SWEEP]);
-      cur = &W.sweep[nxt];
-      nxt ^= 1;
+    int32_t j = 1;
+    while (n_sw > 0 && sweep_step(j)) j++;
+  }
+  // false: nothing left to scan
+  bool sweep_step(int32_t j) {
+    const int32_t sweep_mode = q.sweep_mode;
+    const bool push_now = push_ok && !arena_lost;  // an arena overflow mid-sweep: pull only
+    ensure_x(n_sw + (push_now ? n_arena : 0));
+    k_cnt_zero<<<1, 256, 0, c.stream>>>(cnt, 1u << C_X | 1u << C_ACTIVE | 1u << C_OVF | 1u << C_SWEEP | 1u << C_XE,
+                                        nullptr, push_now ? pullc : nullptr, push_now ? 2 * nb : 0);
+    refresh(nullptr, 0);
+    if (push_now) {
+      k_sweep_pull_cost<<<grid_n(n_sw), 256, 0, c.stream>>>(cur->as<uint64_t>(), n_sw, sweep_mode, st, q.gin, pullc);
+      if (n_arena)
+        k_sweep_push_cost<<<grid_n(n_arena), 256, 0, c.stream>>>(W.arena.as<uint64_t>(), n_arena, j, st, q.gout, pullc,
+                                                                  pushc);
+      k_sweep_choose<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(pullc, pushc, int32_t(nb), push_pair, kPushBias16);
     }
+    k_sp_select<<<grid_sel(n_sw), kBlk, 0, c.stream>>>(cur->as<uint64_t>(), n_sw, sweep_mode, st, q.gout, q.gin,
+                                                     W.X.as<uint64_t>(), W.Xdeg.as<int64_t>(), W.cap_x, bf, cnt,
+                                                     push_now ? push_pair : nullptr);
+    if (push_now && n_arena)
+      k_sweep_push_select<<<grid_n(n_arena), 256, 0, c.stream>>>(W.arena.as<uint64_t>(), n_arena, j, st, q.gout, push_pair,
+                                                                  W.X.as<uint64_t>(), W.Xdeg.as<int64_t>(), W.cap_x, cnt);
+    NBG_HIP(hipGetLastError());
+    sync_counters();
+    const int64_t nX = int64_t(hc[C_X]), E = int64_t(hc[C_XE]);
+    if (nX == 0 || E == 0) return false;
+    const int64_t want = std::min<int64_t>(E, q.soft) + 64;
+    reserve(c, W.sweep[nxt], W.cap_sweep[nxt], want, 0);
+    if (!arena_lost) reserve(c, W.arena, W.cap_arena, n_arena + want, n_arena);
+    refresh(&W.sweep[nxt], W.cap_sweep[nxt]);
+    if (q.sweep_chunks) {
+      // chunk counts -> their scan -> chunk table -> one wave per chunk
+      DevBuf ch, choff, chx;
+      ch.alloc(size_t(nX + 1) * 8);
+      choff.alloc(size_t(nX + 1) * 8);
+      k_sp_chunks_n<<<grid_n(nX + 1), 256, 0, c.stream>>>(W.Xdeg.as<int64_t>(), nX, ch.as<int64_t>(), kSwCh);
+      scan_i64(c, ch.as<int64_t>(), choff.as<int64_t>(), nX + 1);
+      const int64_t max_ch = nX + E / kSwCh + 1;
+      chx.alloc(size_t(max_ch) * 4);
+      hipEventRecord(c.ev[2], c.stream);
+      k_chunk_x<<<grid_n(nX), 256, 0, c.stream>>>(choff.as<int64_t>(), nX, chx.as<int32_t>());
+      const int sgrid = int(std::max<int64_t>(1, std::min<int64_t>((max_ch + 3) / 4, 8192)));
+      k_sp_sweep<1><<<sgrid, 256, 0, c.stream>>>(W.X.as<uint64_t>(), choff.as<int64_t>(), chx.as<int32_t>(), nX, q.gout,
+                                                 q.gin, q.d0, q.d1, n, lo, st, bf, cnt);
+      NBG_HIP(hipGetLastError());
+      hipEventRecord(c.ev[3], c.stream);
+    } else {
+      scan_x(nX);
+      launch_expand(nX, E, 1);
+    }
+    sync_counters();
+    record(4, ev_ms(2, 3), nX, E, int64_t(hc[C_SWEEP]), j, 0, uint64_t(nX) * 32 + uint64_t(E) * 6 + hc[C_SWEEP] * 18);
+    if (int64_t(hc[C_ARENA]) > W.cap_arena) arena_lost = true;
+    n_arena = std::min<int64_t>(int64_t(hc[C_ARENA]), W.cap_arena);
+    if (int64_t(hc[C_SWEEP]) > W.cap_sweep[nxt]) {
+      reserve(c, W.sweep[nxt], W.cap_sweep[nxt], int64_t(hc[C_SWEEP]) + 64, 0);
+      const int32_t np = pair_list([](int32_t stt, int32_t, int32_t) { return stt == SP_MET; });
+      set_counter(C_SWEEP, 0);
+      regen(RG_SWEEP, 1, j, np, W.sweep[nxt].as<uint64_t>(), W.cap_sweep[nxt], C_SWEEP);
+      sync_counters();
+    }
+    n_sw = int64_t(hc[C_SWEEP]);
+    cur = &W.sweep[nxt];
+    nxt ^= 1;
+    return true;
+  }
 
-    // results + paths: the path offsets, their total and the longest path on the device (one
-    // counter fetch); state, res, offsets and the walked paths come back with the batch's last
-    // fetch, through the pinned stage when they fit (pageable copies and a stream synchronisation
-    // here cost ~0.1 ms a batch)
-    DevBuf doff, dpath, wk;  // (wk: the walk state, drained by the batch's last fetch)
+  // The path offsets, their total and the longest path on the device (one counter fetch), then
+  // the smallest-vid walk of every pair.
+  void walk() {
     doff.alloc(size_t(nb + 1) * 8);
     k_sp_path_offsets<<<1, 1024, 0, c.stream>>>(st, nb, doff.as<int64_t>(), cnt);
     NBG_HIP(hipGetLastError());
     sync_counters();
-    const int64_t plen = int64_t(hc[C_PLEN]);
+    plen = int64_t(hc[C_PLEN]);
     const int32_t maxL = int32_t(hc[C_MAXL]);
-    if (plen > 0) {
-      dpath.alloc(size_t(plen) * 8);
-      if (c.opt("sp_walk_wg", 0) || nb >= kTileE) {  // a tile stages at most kTileE pair entries
-        k_sp_walk<<<int(nb), kWalkT, 0, c.stream>>>(st, dgs, doff.as<int64_t>(), dpath.as<int64_t>(), gout, d1,
-                                                    vid_of, n, lo, cnt);
-      } else if (maxL >= 2) {
-        // walk state: cur [B], best [B], degrees / offsets [B + 1], tile rows (all pairs' rows <= nnz)
-        const int64_t max_tiles = (cout->nnz + kTileE - 1) / kTileE + nb + 2;
-        const size_t wbytes = size_t(nb) * 4 + 64 + size_t(nb) * 8 + 64 + 2 * (size_t(nb + 1) * 8 + 64) +
-                              size_t(max_tiles) * 4 + 64;
-        wk.alloc(wbytes);
-        Carve cv(wk, "shortest path: walk workspace");
-        int32_t* dcur = cv.take<int32_t>(size_t(nb) * 4);
-        long long* dbest = cv.take<long long>(size_t(nb) * 8);
-        int64_t* wdeg = cv.take<int64_t>(size_t(nb + 1) * 8);
-        int64_t* woff = cv.take<int64_t>(size_t(nb + 1) * 8);
-        int32_t* wtr = cv.take<int32_t>(size_t(max_tiles) * 4);
-        NBG_HIP(hipMemcpyAsync(dcur, dgs, size_t(nb) * 4, hipMemcpyDeviceToDevice, c.stream));
-        size_t tb = 0;
-        NBG_HIP(rocprim::exclusive_scan(nullptr, tb, wdeg, woff, int64_t(0), size_t(nb + 1), rocprim::plus<int64_t>(),
-                                        c.stream));
-        c.ws_tmp.ensure(tb);
-        const int wgrid = int(std::max<int64_t>(1, std::min<int64_t>(256 * 8, max_tiles)));
-        for (int32_t i = 0; i + 1 < maxL; i++) {
-          k_sp_walk_front<<<grid_n(nb + 1, 1 << 20), 256, 0, c.stream>>>(st, i, dcur, gout, wdeg, dbest);
-          NBG_HIP(rocprim::exclusive_scan(c.ws_tmp.p, tb, wdeg, woff, int64_t(0), size_t(nb + 1),
-                                          rocprim::plus<int64_t>(), c.stream));
-          k_tile_rows<kTileE><<<grid_n(nb), 256, 0, c.stream>>>(woff, nb, wtr);
-          k_sp_walk_scan<<<wgrid, kT, 0, c.stream>>>(st, i, dcur, woff, wtr, gout, d1, vid_of, n, lo, dbest);
-          k_sp_walk_pick<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(
-              st, i, dcur, dbest, doff.as<int64_t>(), dpath.as<int64_t>(), c.ht_keys.as<int64_t>(),
-              c.ht_vals.as<int32_t>(), uint64_t(c.ht_cap - 1), c.ht_has_min, c.ht_min_gidx, lo, cnt);
-          NBG_HIP(hipGetLastError());
-        }
+    if (plen <= 0) return;
+    dpath.alloc(size_t(plen) * 8);
+    if (q.walk_wg || nb >= kTileE) {  // a tile stages at most kTileE pair entries
+      k_sp_walk<<<int(nb), kWalkT, 0, c.stream>>>(st, dgs, doff.as<int64_t>(), dpath.as<int64_t>(), q.gout, q.d1,
+                                                  q.vid_of, n, lo, cnt);
+    } else if (maxL >= 2) {
+      // walk state: cur [B], best [B], degrees / offsets [B + 1], tile rows (all pairs' rows <= nnz)
+      const int64_t max_tiles = (q.cout->nnz + kTileE - 1) / kTileE + nb + 2;
+      const size_t wbytes = size_t(nb) * 4 + 64 + size_t(nb) * 8 + 64 + 2 * (size_t(nb + 1) * 8 + 64) +
+                            size_t(max_tiles) * 4 + 64;
+      wk.alloc(wbytes);
+      Carve cv(wk, "shortest path: walk workspace");
+      int32_t* dcur = cv.take<int32_t>(size_t(nb) * 4);
+      long long* dbest = cv.take<long long>(size_t(nb) * 8);
+      int64_t* wdeg = cv.take<int64_t>(size_t(nb + 1) * 8);
+      int64_t* woff = cv.take<int64_t>(size_t(nb + 1) * 8);
+      int32_t* wtr = cv.take<int32_t>(size_t(max_tiles) * 4);
+      NBG_HIP(hipMemcpyAsync(dcur, dgs, size_t(nb) * 4, hipMemcpyDeviceToDevice, c.stream));
+      const int wgrid = int(std::max<int64_t>(1, std::min<int64_t>(256 * 8, max_tiles)));
+      for (int32_t i = 0; i + 1 < maxL; i++) {
+        k_sp_walk_front<<<grid_n(nb + 1, 1 << 20), 256, 0, c.stream>>>(st, i, dcur, q.gout, wdeg, dbest);
+        scan_i64(c, wdeg, woff, nb + 1);
+        k_tile_rows<kTileE><<<grid_n(nb), 256, 0, c.stream>>>(woff, nb, wtr);
+        k_sp_walk_scan<<<wgrid, kT, 0, c.stream>>>(st, i, dcur, woff, wtr, q.gout, q.d1, q.vid_of, n, lo, dbest);
+        k_sp_walk_pick<<<grid_n(nb, 1 << 20), 256, 0, c.stream>>>(st, i, dcur, dbest, doff.as<int64_t>(),
+                                                                  dpath.as<int64_t>(), q.htk, q.htv, q.htm, c.ht_has_min,
+                                                                  c.ht_min_gidx, lo, cnt);
+        NBG_HIP(hipGetLastError());
       }
-      NBG_HIP(hipGetLastError());
     }
+    NBG_HIP(hipGetLastError());
+  }
+
+  // State, res, offsets and the walked paths come back with the batch's last counter fetch,
+  // through the pinned stage when they fit (pageable copies and a stream synchronisation here
+  // cost ~0.1 ms a batch).
+  void fetch() {
     const size_t sb = (size_t(nb) * 8 + 63) & ~size_t(63);  // state + res (adjacent in W.state)
     const size_t ob = (size_t(nb + 1) * 8 + 63) & ~size_t(63);
     const bool staged = c.host_stage && c.host_stage_used == 0 && sb + ob + size_t(plen) * 8 <= kHostStageBytes;
     std::vector<int64_t> hoff_b, hpath_b;
-    int32_t* h_sr = hstate.data();  // [state nb][res nb]
+    int32_t* h_sr = nullptr;  // [state nb][res nb]
     int64_t* h_off = nullptr;
     int64_t* h_path = nullptr;
     if (staged) {
@@ -3630,10 +3810,10 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
       h_off = reinterpret_cast<int64_t*>(hs + sb);
       h_path = reinterpret_cast<int64_t*>(hs + sb + ob);
     } else {
-      hstate.resize(size_t(2 * nb));
-      h_sr = hstate.data();
+      q.hstate.resize(size_t(2 * nb));
       hoff_b.resize(size_t(nb + 1));
       hpath_b.resize(size_t(std::max<int64_t>(plen, 1)));
+      h_sr = q.hstate.data();
       h_off = hoff_b.data();
       h_path = hpath_b.data();
     }
@@ -3644,27 +3824,30 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
     // pageable destinations: hipMemcpyAsync may return before such a copy completes, so the
     // stream is drained before the host reads them
     if (!staged) NBG_HIP(hipStreamSynchronize(c.stream));
-    if (plen > 0 && hc[C_WALKERR])
-      throw Error(NBG_E_UNKNOWN, "shortest path: in-edge keys without mirrored out-edges on a shortest path");
-    const size_t base = hpath.size();
-    hpath.resize(base + size_t(plen));
-    if (plen > 0) memcpy(hpath.data() + base, h_path, size_t(plen) * 8);
-    for (int64_t p = 0; p < nb; p++) {
-      const int32_t L = h_sr[p] == SP_ACTIVE ? -1 : h_sr[nb + p];
-      hres[b0 + size_t(p)] = L;
-      if (L >= 0) {  // the ends: src (also the whole path of src == dst) and dst
-        hpath[base + size_t(h_off[p])] = src[b0 + size_t(p)];
-        if (L > 0) hpath[base + size_t(h_off[p] + L)] = dst[b0 + size_t(p)];
-      }
-      hoff.push_back(hoff.back() + h_off[p + 1] - h_off[p]);
-    }
-    // reset the batch's distance bytes
+    if (plen > 0 && hc[C_WALKERR]) throw PathQuery::walk_error();
+    q.append_batch_results(b0, nb, h_sr, h_off, h_path, plen);
+  }
+
+  // the batch's distance bytes back to 0xFF
+  void reset() {
     if (arena_lost) {
-      NBG_HIP(hipMemsetAsync(c.sp_dist[0].p, 0xFF, 2 * c.sp_dist_bytes, c.stream));
+      q.wipe_dist();
     } else if (n_arena) {
-      k_sp_clear<<<grid_n(n_arena), 256, 0, c.stream>>>(W.arena.as<uint64_t>(), n_arena, d0, d1, n, st);
+      k_sp_clear<<<grid_n(n_arena), 256, 0, c.stream>>>(W.arena.as<uint64_t>(), n_arena, q.d0, q.d1, n, st);
       NBG_HIP(hipGetLastError());
     }
+  }
+};
+
+void PathQuery::run_batches() {
+  c.sp_dirty = true;  // until the last batch's bytes are reset
+  for (size_t b0 = 0; b0 < npairs; b0 += size_t(B)) {
+    const int64_t nb = std::min<int64_t>(B, int64_t(npairs - b0));
+    if (dev && DevBatch{*this, b0, nb}.run()) {
+      c.timing.spec_hops++;  // nbg_timing.spec_hops of a shortest-path call: batches run device-driven
+      continue;
+    }
+    HostBatch{*this, b0, nb}.run();
   }
   hipEventRecord(c.ev[1], c.stream);
   NBG_HIP(hipEventSynchronize(c.ev[1]));
@@ -3672,25 +3855,22 @@ int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int6
   float ms = 0;
   hipEventElapsedTime(&ms, c.ev[0], c.ev[1]);
   c.timing.total_ms = ms;
+}
 
-  auto h = std::make_unique<HostRows>();
-  for (int k = 0; k < 3; k++) {
-    h->types.push_back(NBG_T_VID);
-    h->host.emplace_back(npairs * 8 + 8);
-    h->str_off.push_back(nullptr);
-  }
-  for (size_t i = 0; i < npairs; i++) {
-    memcpy(h->host[0].data() + i * 8, src + i, 8);
-    memcpy(h->host[1].data() + i * 8, dst + i, 8);
-    memcpy(h->host[2].data() + i * 8, &hres[i], 8);
-  }
-  for (int k = 0; k < 3; k++) h->cols.push_back(h->host[size_t(k)].data());
-  h->path_offsets = std::move(hoff);
-  h->path_vids = std::move(hpath);
-  if (h->path_vids.empty()) h->path_vids.push_back(0);  // non-null pointer for an empty result
-  fill_rows(out, std::move(h), int64_t(npairs), false);
-  out->edges_scanned = c.timing.edges_scanned;
+}  // namespace
+
+int32_t shortest_path_run(Ctx& c, int32_t et, const int64_t* src_all, const int64_t* dst_all, size_t npairs_all,
+                          int32_t max_steps, nbg_rows* out) {
+  PathQuery q{c, max_steps, out};
+  q.validate(et);
+  q.choose_pairs(src_all, dst_all, npairs_all);
+  q.size_batch();
+  PoolScope pool_scope(query_pool(c));  // every buffer from here on is a query temporary
+  q.start();
+  q.run_batches();
+  q.hand_out();
   return NBG_OK;
 }
 
 }  // namespace nbg
+
