@@ -380,6 +380,72 @@ int32_t nbg_order_by(nbg_ctx* ctx, const nbg_rows* in, const int32_t* cols, cons
 int32_t nbg_set_op(nbg_ctx* ctx, int32_t op, const nbg_rows* left, const nbg_rows* right,
                    int32_t distinct, int32_t keep_on_device, nbg_rows* out);
 
+/* ---- FETCH PROP ON (FetchVerticesExecutor / FetchEdgesExecutor) ---------------------------
+ * FETCH PROP ON tag vid, ... [YIELD [DISTINCT] ...] and FETCH PROP ON edge src->dst[@rank], ...:
+ * the device replacement of FetchVerticesExecutor::fetchVertices / processResult
+ * (src/graph/FetchVerticesExecutor.cpp:84-196) over QueryVertexPropsProcessor
+ * (src/storage/QueryVertexPropsProcessor.cpp) and of FetchEdgesExecutor::fetchEdges / processResult
+ * (src/graph/FetchEdgesExecutor.cpp:221-330) over QueryEdgePropsProcessor::collectEdgesProps
+ * (src/storage/QueryEdgePropsProcessor.cpp:17-40): a point lookup of every key in the resident
+ * snapshot instead of one RocksDB prefix scan per key.
+ * Keys: n vids, or n (src, dst, rank) triples (rank == NULL: every key has rank 0).  With
+ * keys_on_device = 1 the key arrays are device pointers on this context (columns of a
+ * keep_on_device result of nbg_go, nbg_order_by, nbg_set_op or of these calls); they are read in
+ * place and neither consumed nor modified.
+ * Yields: Expression::encode bytes as for nbg_go.  Only the alias.prop form is legal
+ * (FetchExecutor::prepareYield, FetchExecutor.cpp:13-50): a $^ / $$ / $- / $var node or an
+ * edge-key function (_src(e), ...) is NBG_E_INVALID_ARG ("Only support form of alias.prop in fetch
+ * sentence."), as is a yield list without any prop ("No props declared.").  Vertices: the alias must
+ * be the tag's name (else NBG_E_INVALID_ARG) and prop one of its fields.  Edges: the alias is
+ * ignored, as nbg_go ignores it; prop is a schema field or _src / _dst / _rank, the key props
+ * QueryEdgePropsProcessor::addDefaultProps returns (QueryEdgePropsProcessor.cpp:42-48); _type is
+ * NBG_E_UNSUPPORTED.  An unknown prop is NBG_E_IMPROPER_DATA_TYPE.  Arithmetic, relational and
+ * logical operators and constants over the props run on the device VM unchanged.  n_yields = 0:
+ * every field of the tag / edge schema in schema order (FetchExecutor::setupColumns,
+ * FetchExecutor.cpp:52-80).  More than 16 yields: NBG_E_UNSUPPORTED.
+ * A vid yields a row iff the tag has a row for it in the vid's own part (StorageClient sends the
+ * request to part hash(vid), StorageClient.cpp:238-243); a vid without one is skipped
+ * (FetchVerticesExecutor.cpp:136-145).  This includes vertices no edge names (INSERT VERTEX alone).
+ * With several versions of the row the bytewise-first one is read (collectVertexProps,
+ * QueryBaseProcessor.inl:309-333).  An edge key yields a row iff src's out-edges of edge_type hold
+ * (src, rank, dst) in a row nbg_go would expand (the keys sit in src's own part); of several
+ * versions the bytewise-first one is read ("only use the latest version",
+ * QueryEdgePropsProcessor.cpp:26).  A key with an unknown vid is skipped.
+ * Row order (owned by this build, DESIGN.md divergence 10): the rows come in key input order; the
+ * reference's order is the order its storage RPC responses arrive in.
+ * distinct = 1: the keys are deduplicated first, keeping first occurrences (getDistinctVIDs,
+ * FetchVerticesExecutor.cpp:248-250; EdgeKeyHashSet, FetchEdgesExecutor.cpp:144-172); then the
+ * output rows by value, first occurrence kept, in order (uniqResult, FetchVerticesExecutor.cpp:134-176, FetchEdgesExecutor.cpp:270-312)
+ * under nbg_set_op's row equality.
+ * out: column types are the yields' static result types as for nbg_go (every integer is
+ * NBG_T_VID).  Zero keys or zero matches give n_rows = 0 with n_cols = the yield count and those
+ * types.  In HBM when keep_on_device = 1, else on the host; STRING columns as packed bytes +
+ * n_rows + 1 offsets.  An evaluation error on any emitted row (a field the row lacks included)
+ * fails the call with NBG_E_EVAL, as in nbg_go (GoExecutor.cpp:754-758).
+ * Errors: NBG_E_STATE before finalize; NBG_E_TAG_PROP_NOT_FOUND unknown tag_id; NBG_E_INVALID_ARG
+ * unknown edge type, null pointers with n > 0, a flag outside {0, 1}; NBG_E_UNSUPPORTED 2^32 keys
+ * or more, a negative edge_type (in-edges carry no props).
+ * world_size > 1: every rank passes the same keys and emits the rows of the keys it owns (the
+ * vid's part owner; src's part owner for edges); no collective is issued, and the row-level
+ * DISTINCT is rank-local as in nbg_set_op.
+ * nbg_last_timing then reports total_ms, launches, host_waits and n_hops = 0.  edges_scanned: 0
+ * for vertices; for edges the adjacency entries the lookup read (informational).  host_waits: 3
+ * with keys (the match count, the materialiser's error count together with its STRING byte
+ * totals, the hand-out; the second is skipped without matches), 1 without keys; distinct adds one
+ * for the key dedup and one for the row dedup (more than one row).
+ * Engine option "fetch_search" (tests, measurement): 0 = every row is scanned, 1 = every row is
+ * searched, unset = the hybrid: rows of up to 64 entries are scanned, longer rows are searched
+ * down to a window of 64 entries, which is scanned; option
+ * "fetch_threshold" replaces the 64 (measurement).                                             */
+int32_t nbg_fetch_vertices(nbg_ctx* ctx, int32_t tag_id, const int64_t* vids, size_t n,
+                           int32_t keys_on_device, const uint8_t* const* yields,
+                           const size_t* yield_lens, size_t n_yields, int32_t distinct,
+                           int32_t keep_on_device, nbg_rows* out);
+int32_t nbg_fetch_edges(nbg_ctx* ctx, int32_t edge_type, const int64_t* src, const int64_t* dst,
+                        const int64_t* rank, size_t n, int32_t keys_on_device,
+                        const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields,
+                        int32_t distinct, int32_t keep_on_device, nbg_rows* out);
+
 /* ---- timing of the last call (HIP events on the engine stream) --------------------------- */
 /* one hop of the last nbg_go: mode 0 = top-down expansion of a frontier list, 1 = bottom-up
  * over the transposed CSR.  c[]: top-down {frontier, entries, next frontier, 0, 0, 0};

@@ -379,6 +379,33 @@ int32_t nbg_set_op(nbg_ctx* ctx, int32_t op, const nbg_rows* left, const nbg_row
   });
 }
 
+int32_t nbg_fetch_vertices(nbg_ctx* ctx, int32_t tag_id, const int64_t* vids, size_t n, int32_t keys_on_device,
+                           const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields, int32_t distinct,
+                           int32_t keep_on_device, nbg_rows* out) {
+  return guarded(ctx, [&](Ctx& c) {
+    if (!out || (n && !vids) || (n_yields && (!yields || !yield_lens))) throw Error(NBG_E_INVALID_ARG, "bad arguments");
+    memset(out, 0, sizeof(*out));
+    const int32_t rc = nbg::fetch_vertices_run(c, tag_id, vids, n, keys_on_device, yields, yield_lens, n_yields,
+                                               distinct, keep_on_device, out);
+    nbg::timing_resolve(c);
+    return rc;
+  });
+}
+
+int32_t nbg_fetch_edges(nbg_ctx* ctx, int32_t edge_type, const int64_t* src, const int64_t* dst, const int64_t* rank,
+                        size_t n, int32_t keys_on_device, const uint8_t* const* yields, const size_t* yield_lens,
+                        size_t n_yields, int32_t distinct, int32_t keep_on_device, nbg_rows* out) {
+  return guarded(ctx, [&](Ctx& c) {
+    if (!out || (n && (!src || !dst)) || (n_yields && (!yields || !yield_lens)))
+      throw Error(NBG_E_INVALID_ARG, "bad arguments");
+    memset(out, 0, sizeof(*out));
+    const int32_t rc = nbg::fetch_edges_run(c, edge_type, src, dst, rank, n, keys_on_device, yields, yield_lens,
+                                            n_yields, distinct, keep_on_device, out);
+    nbg::timing_resolve(c);
+    return rc;
+  });
+}
+
 int32_t nbg_last_timing(nbg_ctx* ctx, nbg_timing* out) {
   return guarded(ctx, [&](Ctx& c) {
     if (!out) throw Error(NBG_E_INVALID_ARG, "null out");

@@ -419,6 +419,15 @@ struct TagSpace {
   std::vector<PropCol> cols;  // per field, [n_global]; data int64 bits, present uint8:
                               // 0 none, 1 row of the vid's own part, 2 row of a foreign part only
   DevBuf part;                // int32 [n_global]: the part the vertex's row came from
+  // Tag rows of vertices without edges (no gidx): a rank-local tail behind the gidx space.  Every
+  // column, its presence byte, `part` and `state` have n_global + n_tail entries; entry
+  // n_global + k belongs to tail_vids[k] (sorted ascending).  A tail index is valid for this tag's
+  // columns only: never for vid_of or a CSR.  world > 1: the tail holds the rows of the parts this
+  // rank owns and is not gathered.
+  int64_t n_tail = 0;
+  DevBuf tail_vids;           // int64 [n_tail]
+  DevBuf state;               // uint8 [n_global + n_tail]: the tag's row itself (whatever its fields):
+                              // 0 none, 1 row of the vid's own part, 2 row of a foreign part only
 };
 // flat (tag, prop) table the expression compiler resolves $^.tag.prop / $$.tag.prop against
 struct TagFieldRef {
@@ -683,6 +692,13 @@ int32_t order_by_run(Ctx& c, const nbg_rows& in, const int32_t* cols, const int3
 // setops.hip
 int32_t set_op_run(Ctx& c, int32_t op, const nbg_rows& left, const nbg_rows& right, int32_t distinct,
                    int32_t keep_on_device, nbg_rows* out);
+// fetch.hip
+int32_t fetch_vertices_run(Ctx& c, int32_t tag_id, const int64_t* vids, size_t n, int32_t keys_on_device,
+                           const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields, int32_t distinct,
+                           int32_t keep_on_device, nbg_rows* out);
+int32_t fetch_edges_run(Ctx& c, int32_t edge_type, const int64_t* src, const int64_t* dst, const int64_t* rank, size_t n,
+                        int32_t keys_on_device, const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields,
+                        int32_t distinct, int32_t keep_on_device, nbg_rows* out);
 // comm.cpp
 void comm_alltoallv_bytes(Ctx& c, const void* send, const size_t* send_bytes, const size_t* send_off,
                           void* recv, const size_t* recv_bytes, const size_t* recv_off);

@@ -119,6 +119,7 @@ struct Compiler {
   const std::vector<Field>& fields;
   const std::vector<TagFieldRef>* tags = nullptr;
   const std::vector<Field>* inputs = nullptr;  // $- / $var input columns (graphd)
+  FetchMode* fetch = nullptr;                  // FETCH PROP ON yields
   bool graphd;     // graphd AST semantics (GoExecutor) vs storage-decoded filter
   bool out_bound;
   Program prog;
@@ -179,7 +180,48 @@ struct Compiler {
     push();
     return VT_INT;
   }
+  static int32_t vtype_of(int32_t t) {
+    if (t == NBG_T_DOUBLE || t == NBG_T_FLOAT) return VT_DOUBLE;
+    if (t == NBG_T_BOOL) return VT_BOOL;
+    if (t == NBG_T_STRING) return VT_STR;
+    return VT_INT;
+  }
+  // FETCH PROP ON tag: alias.prop -> the tag's column at the fetched vertex
+  int32_t fetch_tag_prop(const Node& x) {
+    if (x.alias != fetch->tag) {
+      fail(NBG_E_INVALID_ARG, "fetch: yield names tag " + x.alias + ", the sentence fetches " + fetch->tag);
+      return VT_ERR;
+    }
+    for (size_t i = 0; tags && i < tags->size(); i++) {
+      const TagFieldRef& t = (*tags)[i];
+      if (t.tag != x.alias || t.prop != x.prop) continue;
+      emit(P_SRCTAG, 0, int16_t(i));
+      push();
+      fetch->n_props++;
+      return vtype_of(t.type);
+    }
+    fail(NBG_E_IMPROPER_DATA_TYPE, "unknown tag prop " + x.alias + "." + x.prop);
+    return VT_ERR;
+  }
   int32_t gen(const Node& x) {
+    if (fetch && fetch->kind != FETCH_NONE) {
+      switch (x.kind) {
+        case kSourceProp: case kDestProp: case kInputProp: case kVariableProp:
+        case kEdgeRank: case kEdgeDstId: case kEdgeSrcId: case kEdgeType:
+          fail(NBG_E_INVALID_ARG, "Only support form of alias.prop in fetch sentence.");
+          return VT_ERR;
+        case kAliasProp:
+        case kEdgeProp:
+          if (fetch->kind == FETCH_VERTICES) return fetch_tag_prop(x);
+          if (x.prop == "_type") {
+            fail(NBG_E_UNSUPPORTED, "fetch: _type is not supported");
+            return VT_ERR;
+          }
+          fetch->n_props++;
+          break;
+        default: break;
+      }
+    }
     switch (x.kind) {
       case kPrimary: {
         static const int32_t map[4] = {VT_INT, VT_DOUBLE, VT_BOOL, VT_STR};
@@ -331,7 +373,7 @@ struct Compiler {
 // Compiles an encoded expression.  Returns NBG_OK or an error code (msg filled).
 int32_t compile_expr(const uint8_t* buf, size_t len, const std::vector<Field>& fields, bool graphd,
                      bool out_bound, Program* out, std::string* msg, const std::vector<TagFieldRef>* tags,
-                     const std::vector<Field>* inputs) {
+                     const std::vector<Field>* inputs, FetchMode* fetch) {
   std::unique_ptr<Node> root;
   try {
     Cur c{buf, buf + len};
@@ -344,6 +386,7 @@ int32_t compile_expr(const uint8_t* buf, size_t len, const std::vector<Field>& f
   Compiler cc(fields, graphd, out_bound);
   cc.tags = tags;
   cc.inputs = inputs;
+  cc.fetch = fetch;
   for (int i = 0; i < kMaxConsts; i++) cc.prog.ctype[i] = -1;
   cc.prog.result_type = cc.gen(*root);
   if (cc.code != NBG_OK) {
@@ -361,6 +404,15 @@ Program program_dst() {
   p.n = 1;
   p.ins[0] = Ins{P_DST, 0, 0};
   p.result_type = VT_INT;
+  return p;
+}
+
+Program program_prop(uint8_t op, int16_t arg, int32_t field_type) {
+  Program p;
+  for (int i = 0; i < kMaxConsts; i++) p.ctype[i] = -1;
+  p.n = 1;
+  p.ins[0] = Ins{op, 0, arg};
+  p.result_type = Compiler::vtype_of(field_type);
   return p;
 }
 

@@ -67,10 +67,23 @@ struct FastPred {
   int64_t k = 0;
 };
 
+// FETCH PROP ON yields (FetchExecutor.cpp:35-47): only alias.prop nodes are legal.  FETCH_VERTICES:
+// the alias must be `tag` and the prop resolves to P_SRCTAG of that tag; FETCH_EDGES: the alias is
+// ignored (the GO rule) and `_type` is not supported.  n_props counts the prop nodes compiled.
+enum FetchKind : int32_t { FETCH_NONE = 0, FETCH_VERTICES = 1, FETCH_EDGES = 2 };
+struct FetchMode {
+  int32_t kind = FETCH_NONE;
+  std::string tag;
+  int32_t n_props = 0;
+};
+
 // expr.cpp
 int32_t compile_expr(const uint8_t* buf, size_t len, const std::vector<Field>& fields, bool graphd,
                      bool out_bound, Program* out, std::string* msg,
-                     const std::vector<TagFieldRef>* tags = nullptr, const std::vector<Field>* inputs = nullptr);
+                     const std::vector<TagFieldRef>* tags = nullptr, const std::vector<Field>* inputs = nullptr,
+                     FetchMode* fetch = nullptr);
+// a one-instruction program pushing edge prop column `arg` (P_PROP) or tag column `arg` (P_SRCTAG)
+Program program_prop(uint8_t op, int16_t arg, int32_t field_type);
 Program program_dst();
 FastPred classify_pred(const Program& p, const std::vector<Field>& fields);
 

@@ -85,5 +85,30 @@ uint64_t expand_bytes(int64_t nF, int64_t E, int pred_width, int mode);
 int32_t column_result_type(int32_t t);
 // the EXP_FLAGS expansion: a.flags[slot] = the edge at that slot passes the predicate
 void expand_flags(Ctx& c, ExpandArgs a, int pk, const FastArgs& fp, const Program* dprog, const EvalEnv& env, int64_t E);
+// the YIELD materialiser (k_materialize, k_str_pack) over n rows (rows_src[i] + lo = the row's src
+// gidx, rows_edge[i] = its edge in env's CSR; rows_edge == nullptr: vertex rows, whose programs hold
+// only P_SRCTAG and constants).  out: one column per program, STRING columns as packed bytes + n + 1
+// offsets, ready for hand_out_rows.  An evaluation error on any row throws NBG_E_EVAL (err_what).
+constexpr int kMaxYieldCols = 16;  // YieldArgs::cols (traverse.hip kMaxYields)
+struct YieldOut {
+  std::vector<int32_t> types;  // NBG_T_*
+  std::vector<DevBuf> dev, off;
+  std::vector<int64_t> str_bytes;
+};
+void yield_rows(Ctx& c, const std::vector<Program>& progs, const EvalEnv& env, const int32_t* rows_src,
+                const int64_t* rows_edge, int64_t lo, int64_t n, const char* err_what, YieldOut& out);
+
+// ---- defined in setops.hip ----
+// one column of a table in HBM (row_gather.h's InCol for callers in another translation unit)
+struct TableCol {
+  int32_t type;  // NBG_T_*
+  const void* data;
+  const int64_t* off;  // STRING
+  int64_t str_bytes;
+};
+// the first row of every class of equal rows (nbg_set_op's row equality), as row numbers in input
+// order in idx: UNION DISTINCT's hash build and probe over one table.  n > 0; returns their count
+// (one host wait)
+int64_t distinct_first_rows(Ctx& c, const std::vector<TableCol>& cols, int64_t n, DevBuf& idx);
 
 }  // namespace nbg

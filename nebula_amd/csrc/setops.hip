@@ -410,6 +410,20 @@ int32_t set_op_impl(Ctx& c, int32_t op, const nbg_rows& lin, const nbg_rows& rin
 
 }  // namespace
 
+// FETCH PROP ON ... DISTINCT (fetch.hip) deduplicates its keys and its rows with the UNION DISTINCT
+// machinery: hash, build, probe PM_FIRST over the one table
+int64_t distinct_first_rows(Ctx& c, const std::vector<TableCol>& cols, int64_t n, DevBuf& idx) {
+  SetTable t;
+  t.n = n;
+  for (const TableCol& tc : cols) t.cols.push_back(InCol{tc.type, tc.data, tc.off, tc.str_bytes});
+  t.describe(c);
+  SetWork w(c);
+  DevBuf hashes, table;
+  w.hash(t, hashes);
+  const uint32_t capmask = w.build(t, hashes, table);
+  return w.select(t, t, hashes, table, capmask, PM_FIRST, idx);
+}
+
 int32_t set_op_run(Ctx& c, int32_t op, const nbg_rows& left, const nbg_rows& right, int32_t distinct,
                    int32_t keep_on_device, nbg_rows* out) {
   if (op != NBG_SET_UNION && op != NBG_SET_INTERSECT && op != NBG_SET_MINUS)

@@ -1993,14 +1993,17 @@ static void build_tag_columns(Ctx& c) {
     std::vector<int32_t> win(size_t(std::max<int64_t>(ng, 1)), -1);
     std::vector<uint8_t> wstate(size_t(std::max<int64_t>(ng, 1)), 0);  // 1 own part, 2 foreign part
     std::vector<int32_t> tpart(size_t(std::max<int64_t>(ng, 1)), 0);
-    if (n > 0 && ng > 0) {
+    std::vector<int64_t> tail_vids;
+    if (n > 0) {
       DevBuf dg;
       dg.alloc(size_t(n) * 4);
-      lookup_gidx(c, ts.stage.src.as<int64_t>(), dg.as<int32_t>(), n);
       const size_t nn = static_cast<size_t>(n);
-      std::vector<int32_t> g(nn), part(nn);
+      std::vector<int32_t> g(nn, -1), part(nn);
       std::vector<int64_t> vid(nn), ver(nn), seq(nn);
-      NBG_HIP(hipMemcpyAsync(g.data(), dg.p, size_t(n) * 4, hipMemcpyDeviceToHost, c.stream));
+      if (ng > 0) {  // (no edge at all: no vertex map, every row is a tail row)
+        lookup_gidx(c, ts.stage.src.as<int64_t>(), dg.as<int32_t>(), n);
+        NBG_HIP(hipMemcpyAsync(g.data(), dg.p, size_t(n) * 4, hipMemcpyDeviceToHost, c.stream));
+      }
       NBG_HIP(hipMemcpyAsync(part.data(), ts.stage.part.p, size_t(n) * 4, hipMemcpyDeviceToHost, c.stream));
       NBG_HIP(hipMemcpyAsync(vid.data(), ts.stage.src.p, size_t(n) * 8, hipMemcpyDeviceToHost, c.stream));
       NBG_HIP(hipMemcpyAsync(ver.data(), ts.stage.ver.p, size_t(n) * 8, hipMemcpyDeviceToHost, c.stream));
@@ -2013,9 +2016,21 @@ static void build_tag_columns(Ctx& c) {
       // world > 1: a rank keeps only its owned slice (replicate_owned gathers slices); a row in a
       // foreign part held by another rank is not visible there (getBound on that part only)
       const int64_t olo = c.owned_lo(), ohi = c.owned_hi();
+      // vids outside every edge have no gidx: their own-part rows (on the rank owning that part)
+      // go to the tag's tail under the same winner rule (FETCH PROP ON reads them)
+      std::map<int64_t, int32_t> orphan;
       for (int64_t i = 0; i < n; i++) {
         int32_t gi = g[size_t(i)];
-        if (gi < 0 || (c.sharded && (gi < olo || gi >= ohi))) continue;
+        if (gi < 0) {
+          if (foreign(i) || (c.sharded && owner_of_part(part[size_t(i)], c.world) != c.rank)) continue;
+          auto ins = orphan.emplace(vid[size_t(i)], int32_t(i));
+          if (ins.second) continue;
+          int32_t& w = ins.first->second;
+          uint64_t a = __builtin_bswap64(uint64_t(ver[size_t(i)])), b = __builtin_bswap64(uint64_t(ver[size_t(w)]));
+          if (a < b || (a == b && seq[size_t(i)] > seq[size_t(w)])) w = int32_t(i);
+          continue;
+        }
+        if (c.sharded && (gi < olo || gi >= ohi)) continue;
         int32_t& w = win[size_t(gi)];
         if (w < 0) {
           w = int32_t(i);
@@ -2039,14 +2054,35 @@ static void build_tag_columns(Ctx& c) {
         wstate[size_t(gi)] = foreign(w) ? 2 : 1;
         tpart[size_t(gi)] = part[size_t(w)];
       }
+      // the tail: entry ng + k = the k-th orphan vid in ascending order
+      win.resize(size_t(ng));
+      wstate.resize(size_t(ng));
+      tpart.resize(size_t(ng));
+      for (const auto& o : orphan) {
+        tail_vids.push_back(o.first);
+        win.push_back(o.second);
+        wstate.push_back(1);
+        tpart.push_back(part[size_t(o.second)]);
+      }
+      if (win.empty()) {
+        win.push_back(-1);
+        wstate.push_back(0);
+        tpart.push_back(0);
+      }
     }
-    DevBuf dwin, dstate;
-    dwin.alloc(size_t(std::max<int64_t>(ng, 1)) * 4);
-    dstate.alloc(size_t(std::max<int64_t>(ng, 1)));
-    ts.part.alloc(size_t(std::max<int64_t>(ng, 1)) * 4);
-    NBG_HIP(hipMemcpyAsync(dwin.p, win.data(), size_t(std::max<int64_t>(ng, 1)) * 4, hipMemcpyHostToDevice, c.stream));
-    NBG_HIP(hipMemcpyAsync(dstate.p, wstate.data(), size_t(std::max<int64_t>(ng, 1)), hipMemcpyHostToDevice, c.stream));
-    NBG_HIP(hipMemcpyAsync(ts.part.p, tpart.data(), size_t(std::max<int64_t>(ng, 1)) * 4, hipMemcpyHostToDevice, c.stream));
+    const int64_t nt = int64_t(tail_vids.size());
+    const int64_t nx = ng + nt;  // the columns' entries: the gidx space, then the tail
+    const size_t nx1 = size_t(std::max<int64_t>(nx, 1));
+    ts.n_tail = nt;
+    ts.tail_vids.alloc(size_t(std::max<int64_t>(nt, 1)) * 8);
+    if (nt) NBG_HIP(hipMemcpyAsync(ts.tail_vids.p, tail_vids.data(), size_t(nt) * 8, hipMemcpyHostToDevice, c.stream));
+    DevBuf dwin;
+    dwin.alloc(nx1 * 4);
+    ts.state.alloc(nx1);
+    ts.part.alloc(nx1 * 4);
+    NBG_HIP(hipMemcpyAsync(dwin.p, win.data(), nx1 * 4, hipMemcpyHostToDevice, c.stream));
+    NBG_HIP(hipMemcpyAsync(ts.state.p, wstate.data(), nx1, hipMemcpyHostToDevice, c.stream));
+    NBG_HIP(hipMemcpyAsync(ts.part.p, tpart.data(), nx1 * 4, hipMemcpyHostToDevice, c.stream));
     NBG_HIP(hipStreamSynchronize(c.stream));  // host vectors are pageable
     ts.cols.clear();
     for (size_t f = 0; f < ts.fields.size(); f++) {
@@ -2054,42 +2090,44 @@ static void build_tag_columns(Ctx& c) {
       pc.name = ts.fields[f].name;
       pc.type = ts.fields[f].type;
       pc.width = 8;
-      pc.data.alloc(size_t(std::max<int64_t>(ng, 1)) * 8);
-      pc.present.alloc(size_t(std::max<int64_t>(ng, 1)));
-      if (n == 0 || ng == 0) {
+      pc.data.alloc(nx1 * 8);
+      pc.present.alloc(nx1);
+      if (n == 0 || nx == 0) {
         NBG_HIP(hipMemsetAsync(pc.data.p, 0, pc.data.bytes, c.stream));
         NBG_HIP(hipMemsetAsync(pc.present.p, 0, pc.present.bytes, c.stream));
       } else {
-        k_tag_gather<<<grid_for(ng), 256, 0, c.stream>>>(dwin.as<int32_t>(), dstate.as<uint8_t>(), ng,
+        k_tag_gather<<<grid_for(nx), 256, 0, c.stream>>>(dwin.as<int32_t>(), ts.state.as<uint8_t>(), nx,
                                                           ts.stage.props[f].as<int64_t>(),
                                                           ts.stage.present[f].as<uint8_t>(), pc.data.as<int64_t>(),
                                                           pc.present.as<uint8_t>());
       }
       if (pc.type == NBG_T_STRING) {
         DevBuf lens;
-        lens.alloc(size_t(ng + 1) * 8);
-        pc.str_off.alloc(size_t(ng + 1) * 8);
-        if (n == 0 || ng == 0) {
+        lens.alloc(size_t(nx + 1) * 8);
+        pc.str_off.alloc(size_t(nx + 1) * 8);
+        if (n == 0 || nx == 0) {
           NBG_HIP(hipMemsetAsync(lens.p, 0, lens.bytes, c.stream));
         } else {
-          k_tag_str_len<<<grid_for(ng + 1), 256, 0, c.stream>>>(dwin.as<int32_t>(), ng, ts.stage.present[f].as<uint8_t>(),
+          k_tag_str_len<<<grid_for(nx + 1), 256, 0, c.stream>>>(dwin.as<int32_t>(), nx, ts.stage.present[f].as<uint8_t>(),
                                                                  ts.stage.str_len[f].as<int64_t>(), lens.as<int64_t>());
         }
-        exclusive_scan_dev<int64_t>(c, lens.as<int64_t>(), pc.str_off.as<int64_t>(), ng + 1);
+        exclusive_scan_dev<int64_t>(c, lens.as<int64_t>(), pc.str_off.as<int64_t>(), nx + 1);
         int64_t total = 0;
-        NBG_HIP(hipMemcpyAsync(&total, pc.str_off.as<int64_t>() + ng, 8, hipMemcpyDeviceToHost, c.stream));
+        NBG_HIP(hipMemcpyAsync(&total, pc.str_off.as<int64_t>() + nx, 8, hipMemcpyDeviceToHost, c.stream));
         NBG_HIP(hipStreamSynchronize(c.stream));
         pc.str_bytes.alloc(size_t(total) + 8);
         if (total > 0)
-          k_tag_str_copy<<<grid_for(ng), 256, 0, c.stream>>>(dwin.as<int32_t>(), ng, c.heap.as<uint8_t>(),
+          k_tag_str_copy<<<grid_for(nx), 256, 0, c.stream>>>(dwin.as<int32_t>(), nx, c.heap.as<uint8_t>(),
                                                               ts.stage.props[f].as<int64_t>(), pc.str_off.as<int64_t>(),
                                                               pc.str_bytes.as<uint8_t>());
         if (c.sharded) {
           // lengths of every rank's owned slice -> global offsets; bytes by owner block
+          // (the tail is rank-local: its lengths stay behind the gathered slices, and its bytes,
+          // which sit behind this rank's owned slice here, move behind every rank's)
           replicate_owned(c, lens, 8);
-          exclusive_scan_dev<int64_t>(c, lens.as<int64_t>(), pc.str_off.as<int64_t>(), ng + 1);
-          std::vector<int64_t> goff(size_t(ng) + 1);
-          NBG_HIP(hipMemcpyAsync(goff.data(), pc.str_off.p, size_t(ng + 1) * 8, hipMemcpyDeviceToHost, c.stream));
+          exclusive_scan_dev<int64_t>(c, lens.as<int64_t>(), pc.str_off.as<int64_t>(), nx + 1);
+          std::vector<int64_t> goff(size_t(nx) + 1);
+          NBG_HIP(hipMemcpyAsync(goff.data(), pc.str_off.p, size_t(nx + 1) * 8, hipMemcpyDeviceToHost, c.stream));
           NBG_HIP(hipStreamSynchronize(c.stream));
           std::vector<size_t> rb(size_t(c.world)), ro(size_t(c.world));
           for (int r = 0; r < c.world; r++) {
@@ -2097,8 +2135,12 @@ static void build_tag_columns(Ctx& c) {
             rb[size_t(r)] = size_t(goff[size_t(c.base[size_t(r) + 1])]) - ro[size_t(r)];
           }
           DevBuf all;
-          all.alloc(size_t(goff[size_t(ng)]) + 8);
-          comm_allgatherv_bytes(c, pc.str_bytes.p, size_t(total), all.p, rb.data(), ro.data());
+          all.alloc(size_t(goff[size_t(nx)]) + 8);
+          const size_t own_bytes = rb[size_t(c.rank)];
+          comm_allgatherv_bytes(c, pc.str_bytes.p, own_bytes, all.p, rb.data(), ro.data());
+          if (size_t(total) > own_bytes)
+            NBG_HIP(hipMemcpyAsync(all.as<uint8_t>() + goff[size_t(ng)], pc.str_bytes.as<uint8_t>() + own_bytes,
+                                   size_t(total) - own_bytes, hipMemcpyDeviceToDevice, c.stream));
           pc.str_bytes = std::move(all);
         }
       }
@@ -2110,7 +2152,10 @@ static void build_tag_columns(Ctx& c) {
       c.tag_refs.push_back(TagFieldRef{ts.name, pc.name, pc.type});
       ts.cols.push_back(std::move(pc));
     }
-    if (c.sharded) replicate_owned(c, ts.part, 4);
+    if (c.sharded) {
+      replicate_owned(c, ts.part, 4);
+      replicate_owned(c, ts.state, 1);
+    }
     NBG_HIP(hipStreamSynchronize(c.stream));
     if (!c.opt("writable", 0)) ts.stage = Staging{};
   }

@@ -1913,12 +1913,14 @@ struct YieldArgs {
   int32_t ncols;
   ColOut cols[kMaxYields];
 };
+// EDGE = false (FETCH PROP ON a tag): a row is a vertex; rows_edge and env.col are never read
+template <bool EDGE = true>
 __global__ void k_materialize(const int32_t* rows_src, const int64_t* rows_edge, int64_t n, const Program* progs,
                               YieldArgs ya, EvalEnv env, int64_t lo, unsigned long long* err) {
   for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) {
-    const int64_t ge = rows_edge[i];
+    const int64_t ge = EDGE ? rows_edge[i] : 0;
     const int32_t sg = int32_t(lo) + rows_src[i];
-    const int32_t dg = env.col[ge];
+    const int32_t dg = EDGE ? env.col[ge] : sg;
     for (int c = 0; c < ya.ncols; c++) {
       Val v = eval_program(progs + c, env, ge, sg, dg);
       if (v.t == VT_ERR || v.t != ya.cols[c].type) {
@@ -2781,6 +2783,76 @@ FastArgs fast_args(const Csr& csr, const FastPred& fpk) {
 // the type a stored column is returned as: FLOAT widens to DOUBLE, VID and TIMESTAMP are INTs
 int32_t column_result_type(int32_t t) {
   return t == NBG_T_FLOAT ? NBG_T_DOUBLE : (t == NBG_T_VID || t == NBG_T_TIMESTAMP) ? NBG_T_INT : t;
+}
+
+static_assert(kMaxYields == kMaxYieldCols, "query_common.h states YieldArgs' column count");
+// The YIELD materialiser for callers outside GO (fetch.hip): programs over a (rows_src, rows_edge)
+// list, STRING columns packed.  One host wait: the error count and the STRING byte totals together.
+void yield_rows(Ctx& c, const std::vector<Program>& progs, const EvalEnv& env, const int32_t* rows_src,
+                const int64_t* rows_edge, int64_t lo, int64_t n, const char* err_what, YieldOut& out) {
+  const size_t ny = progs.size();
+  out.types.clear();
+  out.dev.clear();
+  out.off.clear();
+  out.dev.resize(ny);
+  out.off.resize(ny);
+  out.str_bytes.assign(ny, 0);
+  for (const Program& p : progs) out.types.push_back(result_type(p.result_type));
+  if (n == 0) {
+    for (size_t k = 0; k < ny; k++) out.dev[k].alloc(8);
+    return;
+  }
+  DevBuf dprog, cnt;
+  dprog.alloc(sizeof(Program) * ny);
+  c.h2d(dprog.p, progs.data(), sizeof(Program) * ny);
+  cnt.alloc(8);
+  NBG_HIP(hipMemsetAsync(cnt.p, 0, 8, c.stream));
+  std::vector<DevBuf> slen(ny), addr(ny);
+  YieldArgs ya{};
+  ya.ncols = int32_t(ny);
+  for (size_t k = 0; k < ny; k++) {
+    const int32_t t = progs[k].result_type;
+    DevBuf& b = t == VT_STR ? addr[k] : out.dev[k];
+    b.alloc(size_t(n + 1) * (t == VT_BOOL ? 1 : 8));
+    if (t == VT_STR) {
+      // (a row whose evaluation fails writes nothing: zero lengths keep the scan below defined)
+      slen[k].alloc(size_t(n + 1) * 8);
+      NBG_HIP(hipMemsetAsync(slen[k].p, 0, size_t(n + 1) * 8, c.stream));
+    }
+    ya.cols[k] = ColOut{b.p, t, slen[k].as<int64_t>()};
+  }
+  if (rows_edge)
+    k_materialize<true><<<grid_cap(n), 256, 0, c.stream>>>(rows_src, rows_edge, n, dprog.as<Program>(), ya, env, lo,
+                                                           cnt.as<unsigned long long>());
+  else
+    k_materialize<false><<<grid_cap(n), 256, 0, c.stream>>>(rows_src, nullptr, n, dprog.as<Program>(), ya, env, lo,
+                                                            cnt.as<unsigned long long>());
+  NBG_HIP(hipGetLastError());
+  c.timing.launches++;
+  std::vector<int64_t> totals(ny + 1, 0);
+  for (size_t k = 0; k < ny; k++) {
+    if (progs[k].result_type != VT_STR) continue;
+    out.off[k].alloc(size_t(n + 1) * 8);
+    exclusive_scan_dev<int64_t>(c, slen[k].as<int64_t>(), out.off[k].as<int64_t>(), n + 1);
+    c.timing.launches++;
+    NBG_HIP(hipMemcpyAsync(&totals[k], out.off[k].as<int64_t>() + n, 8, hipMemcpyDeviceToHost, c.stream));
+  }
+  NBG_HIP(hipMemcpyAsync(&totals[ny], cnt.p, 8, hipMemcpyDeviceToHost, c.stream));
+  NBG_HIP(hipStreamSynchronize(c.stream));
+  c.timing.host_waits++;
+  c.host_stage_used = 0;
+  if (totals[ny]) throw Error(NBG_E_EVAL, err_what);
+  for (size_t k = 0; k < ny; k++) {
+    if (progs[k].result_type != VT_STR) continue;
+    out.str_bytes[k] = totals[k];
+    out.dev[k].alloc(size_t(totals[k]) + 8);
+    if (totals[k]) {
+      k_str_pack<<<grid_cap(n), 256, 0, c.stream>>>(addr[k].as<int64_t>(), out.off[k].as<int64_t>(), n,
+                                                    out.dev[k].as<uint8_t>());
+      NBG_HIP(hipGetLastError());
+      c.timing.launches++;
+    }
+  }
 }
 
 // once per snapshot (collective): the out-edges summed over ranks, the largest out-degree and
@@ -3764,7 +3836,7 @@ struct GoQuery {
         k_yield_dst<<<grid_cap(nrows), 256, 0, c.stream>>>(rows_edge, nrows, csr.col.as<int32_t>(),
                                                            c.vid_of.as<int64_t>(), h->dev[0].as<int64_t>());
       } else {
-        k_materialize<<<grid_cap(nrows), 256, 0, c.stream>>>(rows_src, rows_edge, nrows, dprog.as<Program>() + 1, ya,
+        k_materialize<true><<<grid_cap(nrows), 256, 0, c.stream>>>(rows_src, rows_edge, nrows, dprog.as<Program>() + 1, ya,
                                                              env, lo, K.d + kCntYieldErr);
       }
       NBG_HIP(hipGetLastError());

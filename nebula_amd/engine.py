@@ -9,6 +9,11 @@
                            device-resident replacement of src/graph/GoExecutor.cpp:80-782.
 * ``OrderByExecutor``   -- ``... | ORDER BY $-.col [ASC|DESC], ...`` on a result table, the device
                            replacement of src/graph/OrderByExecutor.cpp:70-136.
+* ``SetExecutor``       -- ``A UNION / INTERSECT / MINUS B`` on two result tables (src/graph/SetExecutor.cpp).
+* ``FetchVerticesExecutor`` / ``FetchEdgesExecutor`` -- ``FETCH PROP ON tag vids`` /
+                           ``FETCH PROP ON edge src->dst@rank``, also piped from a result table: a device
+                           point lookup of every key (src/graph/FetchVerticesExecutor.cpp,
+                           FetchEdgesExecutor.cpp).
 * ``FindPathExecutor``  -- FIND SHORTEST PATH FROM ... TO ... OVER ... UPTO N STEPS (the
                            reference's FindExecutor is a stub, src/graph/FindExecutor.cpp:20-22;
                            semantics in include/nebula_amd.h), batched bidirectional BFS.
@@ -179,6 +184,8 @@ class GraphSpace:
         self._options: set[str] = set()
         self._plan_views: dict = {}  # (WHERE bytes, YIELD bytes) -> their C views (go())
         self._last_spec = None  # (argument key, GoSpec, start array) of the last go() call
+        self.tag_ids: dict[str, int] = {}   # registered tag name -> id (FetchVerticesExecutor)
+        self.edge_types: dict[str, int] = {}  # registered edge name -> type (FetchEdgesExecutor)
         self.h = self.L.nbg_ctx_create(device, num_parts, rank, world_size)
         if not self.h:
             raise RuntimeError("nbg_ctx_create failed: no MI355X visible or bad arguments "
@@ -249,10 +256,14 @@ class GraphSpace:
             self.unset_option(k)
 
     # ---- schema + snapshot -----------------------------------------------------------
-    def set_edge_schema(self, edge_type: int, fields: Sequence[tuple[str, int]], ver: int = 0):
+    def set_edge_schema(self, edge_type: int, fields: Sequence[tuple[str, int]], ver: int = 0, name: str | None = None):
+        """`name`: the edge's name, for operators that resolve it (FetchEdgesExecutor); the engine
+        itself addresses edges by type."""
         names = (C.c_char_p * max(len(fields), 1))(*[f.encode() for f, _ in fields])
         types = (C.c_int32 * max(len(fields), 1))(*[t for _, t in fields])
         self._check(self.L.nbg_schema_set_edge(self.h, edge_type, ver, len(fields), names, types))
+        if name is not None:
+            self.edge_types[name] = edge_type
 
     def set_tag_schema(self, tag_id: int, name: str, fields: Sequence[tuple[str, int]], ver: int = 0):
         """Tag schema + name (SchemaManager::getTagSchema / toTagID): enables $^.name.prop and
@@ -260,6 +271,7 @@ class GraphSpace:
         names = (C.c_char_p * max(len(fields), 1))(*[f.encode() for f, _ in fields])
         types = (C.c_int32 * max(len(fields), 1))(*[t for _, t in fields])
         self._check(self.L.nbg_schema_set_tag(self.h, tag_id, name.encode(), ver, len(fields), names, types))
+        self.tag_ids[name] = tag_id
 
     def load_part(self, part: int, pairs):
         kb, koff, vb, voff = pairs if isinstance(pairs, tuple) else pack_kv(pairs)
@@ -533,6 +545,65 @@ class GraphSpace:
         self._check(self.L.nbg_set_op(self.h, int(op), C.byref(lrows), C.byref(rrows), int(distinct),
                                       int(bool(keep_on_device)), C.byref(out)))
         return RowSet(out, holder=_RowsHandle(self.L, out), raw_strings=lraw or rraw)
+
+    @staticmethod
+    def _fetch_key(key, who: str):
+        """One key argument of a fetch call -> (pointer, n, on_device, keepalive): an array, or
+        (rowset, column): a device-resident RowSet's column read in place, or a host one by value."""
+        if isinstance(key, tuple) and len(key) == 2 and isinstance(key[0], RowSet):
+            rs, col = key[0], int(key[1])
+            if rs.types[col] not in (_lib.T_INT, _lib.T_VID, _lib.T_TIMESTAMP):
+                raise ValueError(f"{who}: key column {col} is not an integer column")
+            if rs.on_device:
+                if rs._holder is None or rs._holder.rows is None:
+                    # (a plain go(keep_on_device=True) hands its blocks back at once: keep a GO's
+                    # table with go(..., keep_on_device=True, order_by=[]))
+                    raise ValueError(f"{who}: this device RowSet no longer owns its columns")
+                return C.c_void_p(rs.device_ptrs[col]), rs.n_rows, True, rs
+            key = rs.columns[col]
+        a = np.ascontiguousarray(key, dtype=np.int64)
+        if a.ndim != 1:
+            raise ValueError(f"{who}: keys must be one-dimensional")
+        return _p(a if a.size else np.zeros(1, dtype=np.int64)), len(a), False, a
+
+    @staticmethod
+    def _yield_views(yields):
+        ys = [X.encode(y) for y in yields]
+        bufs = [C.create_string_buffer(y, len(y) + 1) for y in ys]
+        yp = (C.c_void_p * max(len(ys), 1))(*[C.cast(b, C.c_void_p) for b in bufs])
+        yl = (C.c_size_t * max(len(ys), 1))(*[len(y) for y in ys])
+        return yp, yl, len(ys), bufs
+
+    def fetch_vertices(self, tag: int, vids, yields: Iterable = (), distinct: bool = False,
+                       keep_on_device: bool = False) -> RowSet:
+        """FETCH PROP ON tag vids [YIELD [DISTINCT] ...] (nbg_fetch_vertices).  `tag`: the tag id;
+        `vids`: an array or (rowset, column); `yields`: tag.prop expressions (none: every field).
+        Rows come in key order; a vid without a row of the tag is skipped."""
+        ptr, n, on_dev, _keep = self._fetch_key(vids, "fetch_vertices")
+        yp, yl, ny, _bufs = self._yield_views(yields)
+        out = _lib.Rows()
+        self._check(self.L.nbg_fetch_vertices(self.h, int(tag), ptr, n, int(on_dev), yp, yl, ny, int(bool(distinct)),
+                                              int(bool(keep_on_device)), C.byref(out)))
+        return RowSet(out, holder=_RowsHandle(self.L, out))
+
+    def fetch_edges(self, edge_type: int, src, dst, rank=None, yields: Iterable = (), distinct: bool = False,
+                    keep_on_device: bool = False) -> RowSet:
+        """FETCH PROP ON edge src->dst[@rank] [YIELD [DISTINCT] ...] (nbg_fetch_edges).  Each of
+        `src`, `dst`, `rank` is an array or (rowset, column), all on the host or all in HBM;
+        rank None: every key has rank 0.  Rows come in key order; a key that is no edge is skipped."""
+        keys = [self._fetch_key(k, "fetch_edges") for k in ((src, dst) if rank is None else (src, dst, rank))]
+        if len({k[1] for k in keys}) != 1:
+            raise ValueError("fetch_edges: src, dst and rank must have the same length")
+        if len({k[2] for k in keys}) != 1:
+            if keys[0][1]:
+                raise ValueError("fetch_edges: the key arrays must be all on the host or all on the device")
+        rp = keys[2][0] if rank is not None else None
+        yp, yl, ny, _bufs = self._yield_views(yields)
+        out = _lib.Rows()
+        self._check(self.L.nbg_fetch_edges(self.h, int(edge_type), keys[0][0], keys[1][0], rp, keys[0][1],
+                                           int(keys[0][2]), yp, yl, ny, int(bool(distinct)), int(bool(keep_on_device)),
+                                           C.byref(out)))
+        return RowSet(out, holder=_RowsHandle(self.L, out))
 
     def shortest_path(self, src, dst, edge_type: int, max_steps: int = 5) -> "PathResult":
         """Pairwise shortest paths (src[i] -> dst[i]) over edge_type out-edges."""
@@ -853,6 +924,47 @@ class SetExecutor:
             rs = self.space.set_op(self.op, left, right, True, keep_on_device=True)
             return self.space.order_by(rs, [(c, ASC) for c in range(len(rs.types))], keep_on_device)
         return self.space.set_op(self.op, left, right, self.distinct, keep_on_device)
+
+
+class FetchVerticesExecutor:
+    """FETCH PROP ON tag vid, ... | FETCH PROP ON tag $-.col [YIELD [DISTINCT] ...]
+    (FetchVerticesExecutor, src/graph/FetchVerticesExecutor.cpp).  `tag_name` resolves through the
+    space's registered tag schemas (SchemaManager::toTagID); `ref_col`: the input column of a piped
+    sentence ($-.col as an index), else execute() takes the vids themselves."""
+
+    def __init__(self, space: GraphSpace, tag_name: str, yields=(), distinct: bool = False, ref_col: int | None = None):
+        if tag_name not in space.tag_ids:
+            raise ValueError(f"tag {tag_name!r} is not registered")
+        self.space, self.tag_id, self.yields = space, space.tag_ids[tag_name], list(yields)
+        self.distinct, self.ref_col = bool(distinct), ref_col
+
+    def execute(self, keys_or_rowset, keep_on_device: bool = False) -> RowSet:
+        keys = (keys_or_rowset, self.ref_col) if self.ref_col is not None else keys_or_rowset
+        return self.space.fetch_vertices(self.tag_id, keys, self.yields, self.distinct, keep_on_device)
+
+
+class FetchEdgesExecutor:
+    """FETCH PROP ON edge src->dst[@rank], ... | FETCH PROP ON edge $-.s->$-.d[@$-.r]
+    (FetchEdgesExecutor, src/graph/FetchEdgesExecutor.cpp).  `edge_name` resolves through the edge
+    schemas registered with a name; `src_col` / `dst_col` / `rank_col`: the input columns of a piped
+    sentence, where execute() takes the RowSet; with src_col None it takes (src, dst[, rank]) arrays."""
+
+    def __init__(self, space: GraphSpace, edge_name: str, yields=(), distinct: bool = False, src_col: int | None = None,
+                 dst_col: int | None = None, rank_col: int | None = None):
+        if edge_name not in space.edge_types:
+            raise ValueError(f"edge {edge_name!r} is not registered")
+        self.space, self.edge_type, self.yields = space, space.edge_types[edge_name], list(yields)
+        self.distinct, self.src_col, self.dst_col, self.rank_col = bool(distinct), src_col, dst_col, rank_col
+
+    def execute(self, keys_or_rowset, keep_on_device: bool = False) -> RowSet:
+        if self.src_col is not None:
+            rs = keys_or_rowset
+            src, dst = (rs, self.src_col), (rs, self.dst_col)
+            rank = (rs, self.rank_col) if self.rank_col is not None else None
+        else:
+            src, dst, *rest = keys_or_rowset
+            rank = rest[0] if rest else None
+        return self.space.fetch_edges(self.edge_type, src, dst, rank, self.yields, self.distinct, keep_on_device)
 
 
 class FindPathExecutor:
