@@ -246,9 +246,34 @@ int32_t nbg_bound_stats(nbg_ctx* ctx, int32_t edge_type, const int32_t* parts, c
  * without input properties work); upto outside {0, 1} is NBG_E_INVALID_ARG.
  * edges_scanned: without distinct the (step, adjacency entry) pairs examined; with distinct the
  * engine runs a visited-pruned BFS and one final step: sum over k < N of outdeg(B_k), B_k the
- * vertices first reached at hop k-1 (B_1 the distinct starts), plus outdeg(union of the B_k).  */
+ * vertices first reached at hop k-1 (B_1 the distinct starts), plus outdeg(union of the B_k).
+ *
+ * GO ... OVER t REVERSELY (edge_type = -t, t a registered type: the convention of nbg_get_bound;
+ * the reference parses it, parser.yy:512-521, and refuses to run it, GoExecutor.cpp:203-205;
+ * DESIGN.md divergence 11).  edge_type = 0 is NBG_E_INVALID_ARG, -t with t not in the snapshot
+ * NBG_E_INVALID_ARG "edge type not in snapshot", a type without an in CSR NBG_E_UNSUPPORTED.  A
+ * hop expands a frontier vertex v over the in keys (part(v), v, -t, rank, u) of v's own part:
+ * e._src = v, e._dst = u (the far end, the edge's original source), e._rank = the key's rank,
+ * e._type = the alias as always; $^.tag.prop reads v, $$.tag.prop reads u; the default YIELD is
+ * e._dst.  In-bound keys carry no edge schema props: one in WHERE or YIELD is
+ * NBG_E_IMPROPER_DATA_TYPE "in-bound edges have no props", reported like an unknown edge prop of
+ * a forward GO, when the final step runs.  DISTINCT, duplicate starts, $- / $var inputs and the
+ * smallest-root rule, the empty-frontier endings, keep_on_device, sharding by owner and UPTO
+ * (the concatenation of GO k STEPS ... REVERSELY, k = 1 .. N) carry over unchanged.
+ * edges_scanned: as above with in-degrees (the sum of the frontiers' in-degrees; under UPTO
+ * DISTINCT indeg(B_k) and indeg(union)), whichever kernel ran a hop.
+ * Pull hops: a reverse hop from a large frontier scans the out rows instead (nbg::k_rev_pull, hop
+ * mode 6) -- non-final hops, and the final hop of DISTINCT with the lone e._dst yield and no
+ * WHERE -- when the frontier's in-degree sum E over ranks is >= in-entries / rev_bu_div (option,
+ * default 4).  Options bottom_up = 0 or bu_force = -1: never pull; bu_force = 1: always pull
+ * where legal.  Never with $- / $var inputs at steps > 1, nor under UPTO.  A pull is legal only
+ * when the in keys mirror the out keys, one in key (v, -t, rank, u) per out key (u, t, rank, v):
+ * known after gen_rmat; unknown after KV loads and after a commit that changed the type, then
+ * checked exactly on a one-rank context at the first query that would pull (cached until the
+ * next such commit); a sharded KV-loaded space stays unknown and runs top-down.  Without the
+ * mirror bu_force = 1 still runs top-down: the result never depends on these options.          */
 typedef struct {
-  int32_t edge_type;
+  int32_t edge_type;      /* < 0: GO ... OVER -edge_type REVERSELY                              */
   int32_t steps;
   const int64_t* starts;
   size_t n_starts;
@@ -455,6 +480,8 @@ int32_t nbg_fetch_edges(nbg_ctx* ctx, int32_t edge_type, const int64_t* src, con
  * A hop of a GO UPTO ... DISTINCT's pruned BFS (final_hop = 0; kernels names nbg::k_upto_claim,
  * mode 0, or nbg::k_upto_bu, mode 1): c[] = {vertices first reached, their out-degree sum, size
  * of the level expanded, adjacency entries read, 0, 0, 0, 0}; its final step records as above.
+ * mode 6 = a pull hop of GO ... REVERSELY over the out rows (kernels names nbg::k_rev_pull):
+ * c[] = {found, next-hop in-degree sum, 0, rows scanned, entries read, 0, 0, 0}.
  * nbg_shortest_path records one entry per launch instead: mode 2 = BFS expansion, 3 = meet
  * probe, 4 = sweep; c[] = {tuples, adjacency entries, claims, meets so far, iteration,
  * active pairs, 0, 0}; 5 = walk scan (device-driven batches), c[] = {chunks, adjacency

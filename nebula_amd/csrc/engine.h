@@ -402,6 +402,22 @@ struct EdgeSpace {
   // one or two column lines.
   DevBuf brec;
   int64_t brec_rows = 0;
+  // GO ... REVERSELY (edge_type < 0): what the reverse direction's view of a GoQuery reads next
+  // to the in CSR, built by ensure_rev on the type's first REVERSELY query (collective on several
+  // ranks) and dropped wherever the transpose's derived data is, or a commit touches the type.
+  struct Rev {
+    bool built = false;
+    DevBuf ideg;                   // uint32 [owned rows]: in-degree, 0 where in.row_ok == 0 (padded as odeg)
+    int64_t max_ideg_global = -1;  // largest in-degree over all ranks
+    std::vector<int64_t> top_deg;  // prefix sums of the kTopDeg largest in-degrees over all ranks
+    int64_t in_nnz_global = -1;    // in entries of row_ok rows, summed over ranks
+    // do the in keys mirror the out keys (one in entry (v, rank, u) per out entry (u, rank, v))?
+    // 1 known true, 0 known false, -1 unknown.  The same on every rank (ensure_rev combines the
+    // ranks' kv_loaded flags); only a mirrored type may run the pull hop (k_rev_pull).
+    int mirror = -1;
+  } rev;
+  // some tuple of this type came from KV pairs (load / write), not from gen_rmat alone
+  bool kv_loaded = false;
 };
 constexpr int kRecEntries = 14;
 
@@ -675,6 +691,9 @@ void wait_host_word(Ctx& c, const unsigned long long* word, uint64_t seq);
 void resolve_total(Ctx& c);
 // traverse.hip
 int32_t go_run(Ctx& c, const nbg_go_spec& spec, nbg_rows* out);
+// the in keys' derived data of a REVERSELY query, EdgeSpace::rev (collective: every rank calls it
+// at the same point)
+void ensure_rev(Ctx& c, EdgeSpace& es);
 // the out CSR replica and its out-degrees (collective: every rank calls it at the same point)
 void ensure_rep_out(Ctx& c, EdgeSpace& es);
 void timing_reset(Ctx& c);

@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "device_common.h"
+#include "edge_lookup.h"
 #include "engine.h"
 #include "program.h"
 #include "query_common.h"
@@ -29,7 +30,7 @@ namespace nbg {
 namespace {
 
 constexpr int kFetchThreads = 256;
-constexpr int kFetchGroup = 16;          // lanes per edge key
+constexpr int kFetchGroup = kLookupGroup;  // lanes per edge key
 constexpr int64_t kFetchThreshold = 64;  // hybrid: rows longer than this are searched down to a window of it
 
 // ---- vertices -----------------------------------------------------------------------------------
@@ -67,30 +68,19 @@ struct EdgeLookup {
   const int32_t* gd;
   int64_t n;
   const int64_t* row_ptr;
-  const int32_t* col;
-  const int64_t* col_vid;  // or null: vid_of[col[e]]
-  const int64_t* erank;    // or null: every edge has rank 0
+  EdgeRows rows;           // col, col_vid, erank, vid_of and the search window (edge_lookup.h)
   const uint8_t* row_ok;   // or null: every row visible
-  const int64_t* vid_of;
   int64_t lo, n_rows;
-  int64_t window;  // entries the search leaves to the scan: 1 search, INT64_MAX scan, else the threshold
   int32_t* out_src;   // local row of the key's src
   int64_t* out_edge;  // the matching entry
   uint8_t* flag;
   unsigned long long* scanned;  // [0] entries the scans read, [1] entries the searches probed
 };
 
-// One 16-lane group per key.  Inside a row the entries ascend in (bswap64(rank), bswap64(dst vid))
-// compared unsigned (the reference's key order), and the CSR keeps one entry per (rank, dst), so a
-// key matches at most one entry.  A binary search under that order narrows the row to a window of
-// at most `window` entries that holds the match if there is one (every lane of the group runs the
-// same probes: one broadcast address per group); then the group scans the window, col (and rank)
-// 16 entries a step, and a ballot picks the hit.  window = 1: a pure search; window >= the row: a
-// pure scan; the hybrid scans rows up to the threshold whole and searches longer rows down to a
-// threshold-sized window, which spares them the last log2(threshold) dependent probes.  The scan
-// loop's condition is wave-uniform, so the ballot runs with every lane active.
+// One 16-lane group per key: the key's row, then group_find_edge (edge_lookup.h: the binary search
+// under the row's bytewise order down to a window and the window's scan).
 __global__ __launch_bounds__(kFetchThreads) void k_fetch_edge(EdgeLookup a) {
-  const int lane = threadIdx.x & (kWave - 1), sub = lane & (kFetchGroup - 1), grp = lane / kFetchGroup;
+  const int lane = threadIdx.x & (kWave - 1), sub = lane & (kFetchGroup - 1);
   const int64_t groups = int64_t(gridDim.x) * (kFetchThreads / kFetchGroup);
   const int64_t g0 = (int64_t(blockIdx.x) * kFetchThreads + threadIdx.x) / kFetchGroup;
   const int64_t rounds = (a.n + groups - 1) / groups;
@@ -105,7 +95,7 @@ __global__ __launch_bounds__(kFetchThreads) void k_fetch_edge(EdgeLookup a) {
       rk = a.rank ? a.rank[i] : 0;
       dv = a.dst[i];
       // (a CSR without a rank array holds rank 0 only: a key of another rank matches nothing)
-      if (sg >= 0 && dg >= 0 && sg >= a.lo && sg - a.lo < a.n_rows && (a.erank || rk == 0)) {
+      if (sg >= 0 && dg >= 0 && sg >= a.lo && sg - a.lo < a.n_rows && (a.rows.erank || rk == 0)) {
         row = int32_t(sg - a.lo);
         if (!a.row_ok || a.row_ok[row]) {
           beg = a.row_ptr[row];
@@ -113,40 +103,7 @@ __global__ __launch_bounds__(kFetchThreads) void k_fetch_edge(EdgeLookup a) {
         }
       }
     }
-    // the match, if any, is the lower bound of (krk, kdv), which lies in [l, h]: entries below l
-    // are less than the key, entry h (when h < end) is not
-    const uint64_t krk = bswap64(uint64_t(rk)), kdv = bswap64(uint64_t(dv));
-    int64_t l = beg, h = end;
-    while ((h < end ? h + 1 : end) - l > a.window) {
-      const int64_t m = l + ((h - l) >> 1);
-      const uint64_t er = a.erank ? bswap64(uint64_t(a.erank[m])) : 0;
-      bool less = er < krk;
-      if (er == krk) {
-        const int64_t ev = a.col_vid ? a.col_vid[m] : a.vid_of[a.col[m]];
-        less = bswap64(uint64_t(ev)) < kdv;
-      }
-      if (less) l = m + 1;
-      else h = m;
-      probed += sub == 0;
-    }
-    const int64_t wend = h < end ? h + 1 : end;
-    int64_t found = -1, base = l;
-    while (__any(base < wend)) {
-      const int64_t e = base + sub;
-      const bool live = base < wend;
-      const bool hit = live && e < wend && a.col[e] == dg && (!a.erank || a.erank[e] == rk);
-      const unsigned long long m = __ballot(hit);
-      const unsigned gm = unsigned(m >> (grp * kFetchGroup)) & 0xffffu;
-      if (live) {
-        if (sub == 0) scanned += (unsigned long long)min(int64_t(kFetchGroup), wend - base);
-        if (gm) {
-          found = base + (__ffs(int(gm)) - 1);
-          base = wend;
-        } else {
-          base += kFetchGroup;
-        }
-      }
-    }
+    const int64_t found = group_find_edge(a.rows, beg, end, rk, dv, dg, scanned, probed);
     if (sub == 0 && i < a.n) {
       a.flag[i] = found >= 0;
       a.out_src[i] = row;
@@ -362,14 +319,14 @@ int32_t fetch_edges_impl(Ctx& c, EdgeSpace& es, const int64_t* src, const int64_
     a.gd = gd.as<int32_t>();
     a.n = nk;
     a.row_ptr = csr.row_ptr.as<int64_t>();
-    a.col = csr.col.as<int32_t>();
-    a.col_vid = csr.col_vid.as<int64_t>();
-    a.erank = csr.rank.as<int64_t>();
+    a.rows.col = csr.col.as<int32_t>();
+    a.rows.col_vid = csr.col_vid.as<int64_t>();
+    a.rows.erank = csr.rank.as<int64_t>();
     a.row_ok = csr.row_ok.as<uint8_t>();
-    a.vid_of = c.vid_of.as<int64_t>();
+    a.rows.vid_of = c.vid_of.as<int64_t>();
     a.lo = c.owned_lo();
     a.n_rows = std::min<int64_t>(csr.n_rows, c.owned_hi() - c.owned_lo());
-    a.window = mode == 0 ? INT64_MAX : mode == 1 ? 1 : std::max<int64_t>(1, threshold);
+    a.rows.window = mode == 0 ? INT64_MAX : mode == 1 ? 1 : std::max<int64_t>(1, threshold);
     a.out_src = ksrc.as<int32_t>();
     a.out_edge = kedge.as<int64_t>();
     a.flag = flag.as<uint8_t>();
@@ -393,9 +350,9 @@ int32_t fetch_edges_impl(Ctx& c, EdgeSpace& es, const int64_t* src, const int64_
     float ms = 0;
     if (hipEventElapsedTime(&ms, c.ev[6], c.ev[7]) == hipSuccess) c.timing.expand_ms = ms;
     c.timing.expand_launches = 1;
-    const uint64_t rk = a.erank ? 8 : 0;
+    const uint64_t rk = a.rows.erank ? 8 : 0;
     c.timing.expand_bytes = uint64_t(nk) * (8 + (a.rank ? 8 : 0) + 8 + 16 + (a.row_ok ? 1 : 0) + 13) + h[1] * (4 + rk) +
-                            h[2] * ((a.col_vid ? 8 : 12) + rk);
+                            h[2] * ((a.rows.col_vid ? 8 : 12) + rk);
   }
   const EvalEnv env = make_env(c, es, csr, es.type);
   YieldOut y;

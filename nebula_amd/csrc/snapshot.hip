@@ -433,6 +433,8 @@ static void decode_part(Ctx& c, int32_t part, const uint8_t* kb, const uint64_t*
     unsigned long long h[5];
     NBG_HIP(hipMemcpyAsync(h, d, 40, hipMemcpyDeviceToHost, c.stream));
     NBG_HIP(hipStreamSynchronize(c.stream));
+    // (REVERSELY: KV pairs need not come in out / in pairs, as gen_rmat's tuples do)
+    if (int64_t(h[0]) != es.out_stage.n || int64_t(h[1]) != es.in_stage.n) es.kv_loaded = true;
     es.out_stage.n = int64_t(h[0]);  // the marks roll back a refused batch
     es.in_stage.n = int64_t(h[1]);
     if (h[3] != 0)
@@ -516,6 +518,7 @@ static void reset_transpose_derived(EdgeSpace& es) {
   es.bu_in_tiles = es.bu_both_tiles = 0;
   es.brec.release();
   es.brec_rows = 0;
+  es.rev = EdgeSpace::Rev();  // (REVERSELY: in-degrees, their statistics and the mirror state)
 }
 
 // drop everything snapshot_finalize derives from the staged tuples
@@ -2542,6 +2545,7 @@ static bool commit_merge(Ctx& c) {
       es.rep_in = Csr();
       es.has_rep = es.has_rep_out = false;
       es.rep_odeg.release();
+      es.rev = EdgeSpace::Rev();  // the type's keys changed on some rank: in-degrees and mirror state too
     }
     if (out_any && c.opt("bottom_up", 1)) build_transpose(c, es);  // collective on several ranks
     phase("transpose + slabs");

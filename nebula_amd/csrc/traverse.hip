@@ -23,6 +23,7 @@
 #include <rocprim/device/device_select.hpp>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <unordered_map>
 #include <thread>
@@ -30,6 +31,7 @@
 #include <initializer_list>
 
 #include "device_common.h"
+#include "edge_lookup.h"
 #include "engine.h"
 #include "expr_device.h"
 #include "program.h"
@@ -1890,6 +1892,146 @@ __global__ __launch_bounds__(256) void k_upto_bu(const int64_t* __restrict__ trp
   }
   block_add_sums(acc, 4, lds, sums, shards);
 }
+
+// ---- GO ... REVERSELY: the pull form of a reverse hop (GoQuery::hop_rev_pull) ----
+// A reverse hop from the frontier F yields {u : some out-edge u -> v has v in F}.  The top-down
+// form expands F's rows of the in CSR; when F is large this kernel scans the OUT CSR instead
+// (orp / ocol: row = owned src u, entries = global dst index, in key order): every owned row with
+// row_ok stops at its first dst whose bit is set in the frontier bitmap fb (over the whole gidx
+// space, fb_bits bits).  Legal only where the in keys mirror the out keys (EdgeSpace::Rev::mirror).
+// Modelled on k_upto_bu: one wave owns 64 consecutive rows and builds their next-frontier word by
+// ballot (lane 0 stores it: no bitmap atomics); each lane scans its row's first kRevLane entries
+// alone, rows still open are scanned by the whole wave, 64 entries a step, with a ballot exit.
+// There is no vis (a fixed-depth GO reaches rows again).  ideg (a non-final hop): a found row is
+// kept only with in-edges of its own, and the kept rows' in-degrees sum to the next hop's E;
+// null (the final hop): every found row is kept.  n: the owned rows (next's words), n_rows <= n
+// the rows the CSR has.  sums (zeroed by the caller with their shards; block_add_sums):
+// [0] rows found, [1] in-degree sum of the kept, [2] rows kept (next's population), [3] entries
+// read, [4] rows scanned (row_ok and an out-edge).
+constexpr int kRevLane = 4;
+__global__ __launch_bounds__(256) void k_rev_pull(const int64_t* __restrict__ orp, const int32_t* __restrict__ ocol,
+                                                  const uint8_t* __restrict__ row_ok, int64_t n_rows, int64_t n,
+                                                  const uint32_t* __restrict__ fb, int64_t fb_bits,
+                                                  const uint32_t* __restrict__ ideg,
+                                                  unsigned long long* __restrict__ next, unsigned long long* sums,
+                                                  int shards) {
+  __shared__ unsigned long long lds[kSlots * 16];
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
+  const int64_t nwords = (n + 63) / 64;
+  auto in_front = [&](int32_t d) {
+    return d >= 0 && int64_t(d) < fb_bits && ((fb[uint32_t(d) >> 5] >> (uint32_t(d) & 31u)) & 1u) != 0u;
+  };
+  unsigned long long acc[5] = {0, 0, 0, 0, 0};
+  for (int64_t w = wave; w < nwords; w += nwaves) {  // (wave-uniform)
+    const int64_t row = w * 64 + lane;
+    unsigned long long keep = 0;
+    if (w * 64 < n_rows) {
+      const bool open = row < n_rows && (!row_ok || row_ok[row] != 0);
+      int64_t b = 0, e = 0;
+      if (open) b = orp[row], e = orp[row + 1];
+      acc[4] += b < e ? 1u : 0u;
+      bool found = false;
+      for (int i = 0; i < kRevLane; i++) {
+        if (found || b + i >= e) continue;
+        found = in_front(ocol[b + i]);
+        acc[3]++;
+      }
+      unsigned long long pend = __ballot(!found && b + kRevLane < e);
+      while (pend) {
+        const int l = __ffsll((long long)pend) - 1;
+        pend &= pend - 1;
+        const int64_t rb = __shfl(b, l) + kRevLane, re = __shfl(e, l);
+        bool hit = false;
+        for (int64_t p = rb; p < re && !hit; p += 64) {
+          const int64_t i = p + lane;
+          bool h = false;
+          if (i < re) {
+            h = in_front(ocol[i]);
+            acc[3]++;
+          }
+          hit = __ballot(h) != 0ull;
+        }
+        if (lane == l) found = hit;
+      }
+      const uint32_t d = found && ideg ? ideg[row] : 0u;
+      const bool kept = found && (!ideg || d > 0);
+      keep = __ballot(kept);
+      acc[0] += found ? 1u : 0u;
+      acc[1] += d;
+      acc[2] += kept ? 1u : 0u;
+    }
+    if (lane == 0) next[w] = keep;
+  }
+  block_add_sums(acc, 5, lds, sums, shards);
+}
+
+// deg[v] = the row's entries, 0 where row_ok == 0; stats[0] += their sum, stats[1] = their maximum
+__global__ __launch_bounds__(256) void k_row_deg(const int64_t* __restrict__ rp, const uint8_t* __restrict__ row_ok,
+                                                 int64_t n, uint32_t* __restrict__ deg, unsigned long long* stats) {
+  unsigned long long sum = 0, mx = 0;
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < n; v += stride) {
+    const unsigned long long d = row_ok && !row_ok[v] ? 0ull : (unsigned long long)(rp[v + 1] - rp[v]);
+    deg[v] = uint32_t(d);
+    sum += d;
+    mx = max(mx, d);
+  }
+  sum = wave_sum_u64(sum);
+  for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned long long)__shfl_xor((long long)mx, o));
+  if ((threadIdx.x & 63) == 0) {
+    if (sum) atomicAdd(stats, sum);
+    if (mx) atomicMax(stats + 1, mx);
+  }
+}
+
+// Do the in keys mirror the out keys (one rank: local row = gidx)?  One 16-lane group per in
+// entry e of a row_ok in row v -- the key (v, rank, u) -- looks (rank, v) up in out row u with
+// k_fetch_edge's group lookup; miss counts the entries without their out entry (an out row that
+// is not row_ok holds none).  Both CSRs keep one entry per (src, rank, dst), so with equal entry
+// counts over row_ok rows no miss means a bijection.
+__global__ __launch_bounds__(256) void k_mirror_check(const int64_t* __restrict__ irp, const int32_t* __restrict__ icol,
+                                                      const int64_t* __restrict__ irank,
+                                                      const uint8_t* __restrict__ irow_ok, int64_t n_in_rows,
+                                                      int64_t nnz, const int64_t* __restrict__ orp,
+                                                      const uint8_t* __restrict__ orow_ok, int64_t n_out_rows,
+                                                      EdgeRows out, unsigned long long* miss) {
+  const int lane = threadIdx.x & (kWave - 1), sub = lane & (kLookupGroup - 1);
+  const int64_t groups = int64_t(gridDim.x) * (256 / kLookupGroup);
+  const int64_t g0 = (int64_t(blockIdx.x) * 256 + threadIdx.x) / kLookupGroup;
+  const int64_t rounds = (nnz + groups - 1) / groups;
+  unsigned long long scanned = 0, probed = 0, missed = 0;
+  for (int64_t r = 0; r < rounds; r++) {  // (the same trip count in every lane: the lookup's ballots)
+    const int64_t e = r * groups + g0;
+    int64_t beg = 0, end = 0, rk = 0, dv = 0;
+    int32_t dg = -1;
+    bool key = false;
+    if (e < nnz) {
+      // the entry's row: the last v with irp[v] <= e
+      int64_t l = 0, h = n_in_rows;
+      while (h - l > 1) {
+        const int64_t m = l + ((h - l) >> 1);
+        if (irp[m] <= e) l = m;
+        else h = m;
+      }
+      const int64_t v = l;
+      key = !irow_ok || irow_ok[v] != 0;
+      if (key) {
+        const int64_t u = icol[e];
+        rk = irank ? irank[e] : 0;
+        dv = out.vid_of[v];
+        dg = int32_t(v);
+        if (u >= 0 && u < n_out_rows && (!orow_ok || orow_ok[u] != 0) && (out.erank || rk == 0))
+          beg = orp[u], end = orp[u + 1];
+      }
+    }
+    const int64_t found = group_find_edge(out, beg, end, rk, dv, dg, scanned, probed);
+    missed += key && sub == 0 && found < 0;
+  }
+  missed = wave_sum_u64(missed);
+  if (lane == 0 && missed) atomicAdd(miss, missed);
+}
 // DISTINCT over rows with several ranks: rows are shuffled to rank hash(row) % G first
 __global__ void k_flag_dest(const uint32_t* dest, int64_t n, uint32_t p, uint8_t* flag) {
   for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x)
@@ -2860,53 +3002,120 @@ void yield_rows(Ctx& c, const std::vector<Program>& progs, const EvalEnv& env, c
 // same direction decisions and a GO from a few starts knows its first hop's direction before
 // it runs
 constexpr int64_t kTopDeg = 4096;
-void global_degree_stats(Ctx& c, EdgeSpace& es) {
-  const Csr& csr = es.out;
+// deg: this rank's u32 degrees of its n_own rows (null: no degree array, the prefix sums stay
+// unknown); mine: its (entry count, largest degree, flag).  Out: the kTopDeg prefix sums and the
+// entry count, the largest degree (-1: unknown on some rank) and the flags' sum over ranks.
+static void gather_degree_stats(Ctx& c, const uint32_t* deg, std::array<int64_t, 3> mine, std::vector<int64_t>& top_deg,
+                                int64_t& nnz_all, int64_t& max_all, int64_t& flag_all) {
   const size_t G = size_t(c.world);
   const int64_t n_own = c.owned_hi() - c.owned_lo();
-  // this rank's kTopDeg largest out-degrees (0-padded), descending
+  // this rank's kTopDeg largest degrees (0-padded), descending
   DevBuf top;
-  top.alloc(size_t(kTopDeg) * 4 + 16);
+  top.alloc(size_t(kTopDeg) * 4 + 24);
   NBG_HIP(hipMemsetAsync(top.p, 0, size_t(kTopDeg) * 4, c.stream));
-  if (es.odeg.p && n_own > 0) {
+  if (deg && n_own > 0) {
     DevBuf srt;
     srt.alloc(size_t(n_own) * 4);
     size_t tb = 0;
-    NBG_HIP(rocprim::radix_sort_keys_desc(nullptr, tb, es.odeg.as<uint32_t>(), srt.as<uint32_t>(), size_t(n_own), 0, 32,
-                                          c.stream));
+    NBG_HIP(rocprim::radix_sort_keys_desc(nullptr, tb, deg, srt.as<uint32_t>(), size_t(n_own), 0, 32, c.stream));
     c.ws_tmp.ensure(tb);
-    NBG_HIP(rocprim::radix_sort_keys_desc(c.ws_tmp.p, tb, es.odeg.as<uint32_t>(), srt.as<uint32_t>(), size_t(n_own), 0,
-                                          32, c.stream));
+    NBG_HIP(rocprim::radix_sort_keys_desc(c.ws_tmp.p, tb, deg, srt.as<uint32_t>(), size_t(n_own), 0, 32, c.stream));
     NBG_HIP(hipMemcpyAsync(top.p, srt.p, size_t(std::min(n_own, kTopDeg)) * 4, hipMemcpyDeviceToDevice, c.stream));
   }
-  const size_t row = size_t(kTopDeg) * 4 + 16;  // the degrees, then (nnz, max out-degree)
-  std::vector<int64_t> mine = {csr.nnz, es.max_odeg};
-  NBG_HIP(hipMemcpyAsync(top.as<uint8_t>() + size_t(kTopDeg) * 4, mine.data(), 16, hipMemcpyHostToDevice, c.stream));
+  const size_t row = size_t(kTopDeg) * 4 + 24;  // the degrees, then (nnz, largest degree, flag)
+  NBG_HIP(hipMemcpyAsync(top.as<uint8_t>() + size_t(kTopDeg) * 4, mine.data(), 24, hipMemcpyHostToDevice, c.stream));
   std::vector<uint8_t> all(row * G);
   DevBuf da;
   da.alloc(row * G);
   comm_allgather_bytes(c, top.p, row, da.p);
   NBG_HIP(hipMemcpyAsync(all.data(), da.p, row * G, hipMemcpyDeviceToHost, c.stream));
   host_sync(c);
-  int64_t nnz = 0, mx = 0;
+  int64_t nnz = 0, mx = 0, fl = 0;
   std::vector<uint32_t> degs;
   for (size_t r = 0; r < G; r++) {
     const uint8_t* b = all.data() + r * row;
-    int64_t v[2];
-    memcpy(v, b + size_t(kTopDeg) * 4, 16);
+    int64_t v[3];
+    memcpy(v, b + size_t(kTopDeg) * 4, 24);
     nnz += v[0];
     mx = v[1] < 0 || mx < 0 ? -1 : std::max(mx, v[1]);
+    fl += v[2];
     const uint32_t* d = reinterpret_cast<const uint32_t*>(b);
     degs.insert(degs.end(), d, d + kTopDeg);
   }
   std::sort(degs.begin(), degs.end(), std::greater<uint32_t>());
-  es.top_deg.assign(size_t(kTopDeg) + 1, 0);
-  if (es.odeg.p)
-    for (int64_t k = 0; k < kTopDeg; k++) es.top_deg[size_t(k) + 1] = es.top_deg[size_t(k)] + int64_t(degs[size_t(k)]);
+  top_deg.assign(size_t(kTopDeg) + 1, 0);
+  if (deg)
+    for (int64_t k = 0; k < kTopDeg; k++) top_deg[size_t(k) + 1] = top_deg[size_t(k)] + int64_t(degs[size_t(k)]);
   else
-    es.top_deg.clear();  // no degree array: unknown
-  es.out_nnz_global = nnz;
-  es.max_odeg_global = mx;
+    top_deg.clear();  // no degree array: unknown
+  nnz_all = nnz;
+  max_all = mx;
+  flag_all = fl;
+}
+void global_degree_stats(Ctx& c, EdgeSpace& es) {
+  int64_t flag = 0;
+  gather_degree_stats(c, es.odeg.as<uint32_t>(), {es.out.nnz, es.max_odeg, 0}, es.top_deg, es.out_nnz_global,
+                      es.max_odeg_global, flag);
+}
+
+// GO ... REVERSELY: the in-degrees of the owned rows (0 where in.row_ok == 0, padded to whole
+// 128-row tiles like odeg), their statistics over ranks, and the mirror state every rank agrees
+// on: known true when no rank's tuples of the type came from KV pairs (gen_rmat writes an in
+// tuple per out tuple), else unknown.  Collective on several ranks.
+void ensure_rev(Ctx& c, EdgeSpace& es) {
+  if (es.rev.built) return;
+  EdgeSpace::Rev& rv = es.rev;
+  const int64_t n_own = c.owned_hi() - c.owned_lo();
+  const int64_t n_rows = std::min<int64_t>(n_own, es.in.n_rows);
+  const int64_t n_pad = (n_own + 127) / 128 * 128;
+  rv.ideg.alloc(size_t(n_pad + 1) * 4);
+  NBG_HIP(hipMemsetAsync(rv.ideg.p, 0, size_t(n_pad + 1) * 4, c.stream));
+  DevBuf st;
+  st.alloc(16);
+  NBG_HIP(hipMemsetAsync(st.p, 0, 16, c.stream));
+  if (n_rows > 0)
+    k_row_deg<<<grid_cap(n_rows), 256, 0, c.stream>>>(es.in.row_ptr.as<int64_t>(), es.in.row_ok.as<uint8_t>(), n_rows,
+                                                      rv.ideg.as<uint32_t>(), st.as<unsigned long long>());
+  NBG_HIP(hipGetLastError());
+  unsigned long long h[2] = {0, 0};
+  NBG_HIP(hipMemcpyAsync(h, st.p, 16, hipMemcpyDeviceToHost, c.stream));
+  host_sync(c);
+  int64_t kv_ranks = 0;
+  gather_degree_stats(c, rv.ideg.as<uint32_t>(), {int64_t(h[0]), int64_t(h[1]), es.kv_loaded ? 1 : 0}, rv.top_deg,
+                      rv.in_nnz_global, rv.max_ideg_global, kv_ranks);
+  rv.mirror = kv_ranks == 0 ? 1 : -1;
+  rv.built = true;
+}
+
+// the exact mirror check of a one-rank, non-sharded context (k_mirror_check); paid once per
+// commit of the type: the answer is cached in EdgeSpace::Rev::mirror
+static bool check_mirror(Ctx& c, EdgeSpace& es) {
+  const int64_t n = c.n_global;
+  const int64_t n_in = std::min<int64_t>(n, es.in.n_rows), n_out = std::min<int64_t>(n, es.out.n_rows);
+  DevBuf st, scratch;
+  st.alloc(24);
+  scratch.alloc(size_t(std::max<int64_t>(n_out, 1)) * 4);
+  NBG_HIP(hipMemsetAsync(st.p, 0, 24, c.stream));
+  if (n_out > 0)
+    k_row_deg<<<grid_cap(n_out), 256, 0, c.stream>>>(es.out.row_ptr.as<int64_t>(), es.out.row_ok.as<uint8_t>(), n_out,
+                                                     scratch.as<uint32_t>(), st.as<unsigned long long>());
+  if (es.in.nnz > 0 && n_in > 0) {
+    EdgeRows rows{};
+    rows.col = es.out.col.as<int32_t>();
+    rows.col_vid = es.out.col_vid.as<int64_t>();
+    rows.erank = es.out.rank.as<int64_t>();
+    rows.vid_of = c.vid_of.as<int64_t>();
+    rows.window = 64;
+    k_mirror_check<<<grid_cap(es.in.nnz, 256 / kLookupGroup), 256, 0, c.stream>>>(
+        es.in.row_ptr.as<int64_t>(), es.in.col.as<int32_t>(), es.in.rank.as<int64_t>(), es.in.row_ok.as<uint8_t>(), n_in,
+        es.in.nnz, es.out.row_ptr.as<int64_t>(), es.out.row_ok.as<uint8_t>(), n_out, rows,
+        st.as<unsigned long long>() + 2);
+  }
+  NBG_HIP(hipGetLastError());
+  unsigned long long h[3] = {0, 0, 0};
+  NBG_HIP(hipMemcpyAsync(h, st.p, 24, hipMemcpyDeviceToHost, c.stream));
+  host_sync(c);
+  return int64_t(h[0]) == es.rev.in_nnz_global && h[2] == 0;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2920,7 +3129,18 @@ struct GoQuery {
   Ctx& c;
   const nbg_go_spec& s;
   EdgeSpace& es;
+  // GO ... REVERSELY (edge_type < 0): the hops expand the in keys.  The direction's view, chosen
+  // once: csr (es.out / es.in) and D (the forward view aliases the out-degree fields, so forward
+  // queries run the launches they always ran; the reverse view is EdgeSpace::rev).  REVERSELY is
+  // host-driven, one counter fetch per hop: no k_starts_small first hop, no go_rep1, no
+  // speculation chain, no host_direct; its bottom-up form is the pull hop (hop_rev_pull).
+  const bool rev;
   Csr& csr;
+  struct Dir {
+    const uint32_t* deg = nullptr;            // es.odeg / es.rev.ideg
+    const std::vector<int64_t>* top = nullptr;  // es.top_deg / es.rev.top_deg
+    int64_t max_deg_global = -1, nnz_global = 0;
+  } D;
   nbg_rows* out;
   // the query's device-time events too are instrumentation: with hop_timing off none is recorded
   // (an event between two launches leaves ~5.5 us between them on the device)
@@ -3057,7 +3277,8 @@ struct GoQuery {
   std::map<size_t, bool> host_cols;  // columns already in pinned host memory (host_direct)
 
   GoQuery(Ctx& c_, const nbg_go_spec& s_, EdgeSpace& es_, nbg_rows* out_)
-      : c(c_), s(s_), es(es_), csr(es_.out), out(out_), tot_ev(c_.hop_timing), has_where(s_.where_len > 0),
+      : c(c_), s(s_), es(es_), rev(s_.edge_type < 0), csr(s_.edge_type < 0 ? es_.in : es_.out), out(out_),
+        tot_ev(c_.hop_timing), has_where(s_.where_len > 0),
         default_yield(s_.n_yields == 0), upto(s_.upto == 1 && s_.steps > 1) {}
 
   // WHERE / YIELD programs, the input table's columns (validated here, uploaded once the starts
@@ -3077,7 +3298,7 @@ struct GoQuery {
     }
     const std::vector<Field>* inf = in_fields.empty() ? nullptr : &in_fields;
     if (has_where) {
-      int32_t rc = compile_expr(s.where, s.where_len, es.fields, true, true, &where, &msg, &c.tag_refs, inf);
+      int32_t rc = compile_expr(s.where, s.where_len, es.fields, true, !rev, &where, &msg, &c.tag_refs, inf);
       if (rc == NBG_E_UNSUPPORTED || rc == NBG_E_INVALID_ARG) throw Error(rc, "WHERE: " + msg);
       if (rc != NBG_OK) {
         deferred = rc;
@@ -3090,7 +3311,7 @@ struct GoQuery {
       if (s.n_yields > size_t(kMaxYields)) throw Error(NBG_E_UNSUPPORTED, "too many YIELD columns");
       for (size_t i = 0; i < s.n_yields; i++) {
         Program p{};
-        int32_t rc = compile_expr(s.yields[i], s.yield_lens[i], es.fields, true, true, &p, &msg, &c.tag_refs, inf);
+        int32_t rc = compile_expr(s.yields[i], s.yield_lens[i], es.fields, true, !rev, &p, &msg, &c.tag_refs, inf);
         if (rc == NBG_E_UNSUPPORTED || rc == NBG_E_INVALID_ARG) throw Error(rc, "YIELD: " + msg);
         if (rc != NBG_OK && deferred == NBG_OK) {
           deferred = rc;
@@ -3110,7 +3331,8 @@ struct GoQuery {
     if (deferred == NBG_OK) {
       fpk = has_where ? classify_pred(where, es.fields) : FastPred{};
       fp = fast_args(csr, fpk);
-      pred_bu = pred_runs_bottom_up(fpk, fp, es);
+      // (REVERSELY: a legal WHERE reads vertex or input props only; the pull hop evaluates none)
+      pred_bu = rev ? !has_where : pred_runs_bottom_up(fpk, fp, es);
       fin_spec = s.distinct && lone_dst && pred_bu;
     }
   }
@@ -3133,24 +3355,30 @@ struct GoQuery {
     bitsB = c.ws_bits_recv.as<uint32_t>();
     uint16_t* bits16 = c.ws_bits_send.as<uint16_t>();  // frontier bitmap written by k_compact
     row_ptr = csr.row_ptr.as<int64_t>();
-    bu_ok = es.has_tr && c.opt("bottom_up", 1) != 0;
-    bu_div = std::max<int64_t>(1, c.opt("bu_div", 4));
+    if (rev) {
+      ensure_rev(c, es);
+      if (c.opt("rev_mirror_recheck", 0) != 0 && !c.sharded) es.rev.mirror = -1;  // (measurement)
+    }
+    // (REVERSELY: the pull hop needs mirrored keys -- known, or checked on one rank by want_bu)
+    bu_ok = (rev ? es.rev.mirror == 1 || (es.rev.mirror < 0 && !c.sharded) : es.has_tr) && c.opt("bottom_up", 1) != 0;
+    bu_div = std::max<int64_t>(1, rev ? c.opt("rev_bu_div", 4) : c.opt("bu_div", 4));
     bu_force = c.opt("bu_force", 0);
     row_ok = csr.row_ok.as<uint8_t>();
     ns = int64_t(s.n_starts);
     c.ws_starts.ensure(size_t(std::max<int64_t>(ns, 1)) * 12 + 64);
     int64_t* d_starts = c.ws_starts.as<int64_t>();
     d_sg = reinterpret_cast<int32_t*>(d_starts + std::max<int64_t>(ns, 1));
-    if (es.out_nnz_global < 0) global_degree_stats(c, es);
+    if (!rev && es.out_nnz_global < 0) global_degree_stats(c, es);
+    if (rev) D = Dir{es.rev.ideg.as<uint32_t>(), &es.rev.top_deg, es.rev.max_ideg_global, es.rev.in_nnz_global};
+    else D = Dir{es.odeg.as<uint32_t>(), &es.top_deg, es.max_odeg_global, es.out_nnz_global};
     // a first hop from ns starts is certainly top-down when even the ns largest out-degrees sum
     // below the bottom-up threshold
-    const int64_t deg_bound = ns < int64_t(es.top_deg.size()) ? es.top_deg[size_t(ns)]
-                              : es.max_odeg_global >= 0       ? ns * es.max_odeg_global
-                                                              : INT64_MAX;
-    const bool td1_certain =
-        !bu_ok || bu_force < 0 || (bu_force == 0 && deg_bound < es.out_nnz_global / bu_div);
+    const int64_t deg_bound = ns < int64_t(D.top->size()) ? (*D.top)[size_t(ns)]
+                              : D.max_deg_global >= 0     ? ns * D.max_deg_global
+                                                          : INT64_MAX;
+    const bool td1_certain = !bu_ok || bu_force < 0 || (bu_force == 0 && deg_bound < D.nnz_global / bu_div);
     fast1 = ns > 0 && ns <= kSmallStarts && s.steps >= 2 && td1_certain && !(uses_input && s.steps > 1) &&
-            c.opt("starts_small", 1) != 0 && !upto;
+            c.opt("starts_small", 1) != 0 && !upto && !rev;
     multi = c.sharded;
     ks = multi ? 1 : int(std::min<int64_t>(std::max<int64_t>(c.opt("sum_shards", kSumShards), 1), kSumShards));
     // the small-start path's one block reads the starts from coherent pinned host memory (the
@@ -3165,7 +3393,8 @@ struct GoQuery {
     }
     F = c.ws_front[0].as<int32_t>();
     nset_global = ns;
-    map_bound = es.has_tr && es.bu_in_tiles > 0 ? std::min<int64_t>(n_own, es.bu_in_tiles * 128) : n_own;
+    // (REVERSELY: the marks are srcs, rows with an out-edge: the owned range)
+    map_bound = !rev && es.has_tr && es.bu_in_tiles > 0 ? std::min<int64_t>(n_own, es.bu_in_tiles * 128) : n_own;
     rep1 = fast1 && multi && bu_ok && c.opt("compact_list", 0) == 0 && es.odeg.p && c.opt("go_rep1", 1) != 0;
     csr1 = rep1 ? &es.rep_out : &csr;
     if (rep1) {
@@ -3192,14 +3421,14 @@ struct GoQuery {
     if (!counted) {
       k_list_starts<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, row_ptr, row_ok, F, K.d);
     } else {
-      if (!c.sharded && es.odeg.p) {
+      if (!c.sharded && D.deg) {
         // one rank: dedup the starts through the frontier bitmap itself (a few hundred atomics)
         // instead of marking the byte map and compacting the whole vertex space
         NBG_HIP(hipMemsetAsync(bits16, 0, c.ws_bits_send.bytes, c.stream));
-        k_starts_bits<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, es.odeg.as<uint32_t>(), bitsA, F, K.d);
+        k_starts_bits<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, D.deg, bitsA, F, K.d);
       } else {
         k_mark_gidx<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, map);
-        launch_compact(c, map, lo, n_own, row_ptr, row_ok, 1, F, bits16, K.d, es.odeg.as<uint32_t>());
+        launch_compact(c, map, lo, n_own, row_ptr, row_ok, 1, F, bits16, K.d, D.deg);
       }
       if (!s.distinct)
         k_starts_degree<<<grid_cap(ns), 256, 0, c.stream>>>(d_sg, ns, lo, hi, row_ptr, row_ok, K.d + kCntHop1Rows);
@@ -3306,9 +3535,9 @@ struct GoQuery {
       env.in_mask = cap - 1;
       env.iprops = in_tab.as<PropDev>();
     }
-    host_direct = !s.keep_on_device && c.opt("host_direct", 1) != 0;
-    spec_ok = bu_ok && !multi_root && bu_force >= 0 && c.opt("bu_spec", 1) != 0 && !upto;
-    spec_thr = bu_force > 0 ? 1ull : (unsigned long long)std::max<int64_t>(1, es.out_nnz_global / bu_div);
+    host_direct = !s.keep_on_device && c.opt("host_direct", 1) != 0 && !rev;
+    spec_ok = bu_ok && !multi_root && bu_force >= 0 && c.opt("bu_spec", 1) != 0 && !upto && !rev;
+    spec_thr = bu_force > 0 ? 1ull : (unsigned long long)std::max<int64_t>(1, D.nnz_global / bu_div);
   }
 
   // the frontier as a list: compacts the bitmap when only that exists
@@ -3338,8 +3567,14 @@ struct GoQuery {
     off_ready = true;
   }
   // direction choice is global (every rank must take the same branch: bottom-up allgathers)
-  bool want_bu(int64_t eg) const {  // (multi-step roots need every in-edge: top-down only)
-    return eg > 0 && bu_ok && !multi_root && bu_force >= 0 && (bu_force > 0 || eg >= es.out_nnz_global / bu_div);
+  // (REVERSELY: bottom-up is the pull hop, for mirrored keys only -- an unknown mirror state is
+  // settled here, at the first query that would pull, on one rank -- and never under UPTO)
+  bool want_bu(int64_t eg) {  // (multi-step roots need every in-edge: top-down only)
+    const bool w = eg > 0 && bu_ok && !multi_root && bu_force >= 0 && (bu_force > 0 || eg >= D.nnz_global / bu_div);
+    if (!w || !rev) return w;
+    if (upto) return false;
+    if (es.rev.mirror < 0) es.rev.mirror = !c.sharded && check_mirror(c, es) ? 1 : 0;
+    return es.rev.mirror == 1;
   }
   // the start frontier's degree scan and its out-degree sum over ranks
   void first_degrees() {
@@ -3616,6 +3851,7 @@ struct GoQuery {
 
   // a host-chosen bottom-up hop: frontier bitmap in, next frontier bitmap out
   void hop_bottom_up(int32_t step) {
+    if (rev) return hop_rev_pull();
     const uint32_t* fb = global_bits(c, bitsA);
     const BuLaunch L = timed_bu(c.timing.n_hops, [&] {
       return launch_bu_lean(c, es, fb, bitsB, es.odeg.as<uint32_t>(), PK_NONE, no_fp, -1, K.d, step > 1);
@@ -3629,6 +3865,61 @@ struct GoQuery {
     // ensure_list needs no round trip; several ranks: the local population is read back
     if (multi) adopt_bu(K.h, -1, int64_t(K.h[kCntGlobal]), int64_t(K.h[kCntGlobal + 1]));
     else adopt_bu(K.h, int64_t(K.h[kHopFound]), int64_t(K.h[kHopFound]), int64_t(K.h[kHopDegSum]));
+  }
+
+  // REVERSELY: a pull hop (k_rev_pull over the out rows): frontier bitmap in, next frontier bitmap
+  // out, one counter fetch.  final (DISTINCT _dst): every found row is kept and its vid written to
+  // vout (launch_bits_vids, as final_distinct_dst's bottom-up branch does); returns the row count.
+  // The hop's sums land sharded at [kCntUpto, kCntUpto + 5), the output count at kCntList.
+  int64_t rev_pull(bool final, void* vout) {
+    const uint32_t* fb = global_bits(c, bitsA);
+    NBG_HIP(hipMemsetAsync(K.d, 0, kShardStride * size_t(ks) * 8, c.stream));
+    if (ks > 1) shards_dirty = true;
+    hop_words_stale = false;  // (the memset cleared the block)
+    const int64_t rows = std::min<int64_t>(n_own, es.out.n_rows);
+    const int grid = grid_cap((n_own + 63) / 64 * 64, 256, int(std::max<int64_t>(1, c.opt("upto_grid", 4096))));
+    const size_t ia = timing_event(c);
+    k_rev_pull<<<grid, 256, 0, c.stream>>>(es.out.row_ptr.as<int64_t>(), es.out.col.as<int32_t>(),
+                                           es.out.row_ok.as<uint8_t>(), rows, n_own, fb, c.n_global,
+                                           final ? nullptr : D.deg, reinterpret_cast<unsigned long long*>(bitsB),
+                                           K.d + kCntUpto, ks);
+    NBG_HIP(hipGetLastError());
+    const size_t ik = timing_event(c);
+    if (final) {
+      launch_bits_vids(c, bitsB, n_own, lo, vout, K.d + kCntList, nullptr);
+      NBG_HIP(hipGetLastError());
+    }
+    const size_t ib = final ? timing_event(c) : ik;
+    c.tpend.push_back(Ctx::PendingTime{ia, ib, c.timing.n_hops, 0});
+    c.tpend.push_back(Ctx::PendingTime{ia, ik, c.timing.n_hops, 1});
+    if (multi && !final) dev_allsum(c, K.d, {kCntUpto, kCntUpto + 1}, K.d + kCntGlobal);
+    fetch_counters(c, K.d, kCntUpto + 5, K.h, nullptr, ks);
+    const unsigned long long* h = K.h + kCntUpto;
+    const int64_t n_out = final ? int64_t(K.h[kCntList]) : 0;
+    c.timing.expand_launches++;
+    c.timing.bu_steps++;
+    // the byte model: a row_ptr pair (+ the row_ok byte) per owned row, 4 B per entry
+    // read, the in-degree of every found row (non-final), the next word per 64 rows; the frontier
+    // words are gathered (not counted: they stay in cache); final: + the output (next bits once,
+    // vid_of read + vid written)
+    const uint64_t kb = uint64_t(rows) * (8 + (es.out.row_ok.p ? 1 : 0)) + h[3] * 4 + (final ? 0 : h[0] * 4) +
+                        uint64_t(n_own) / 8;
+    c.timing.expand_bytes += kb + (final ? uint64_t(n_own) / 8 + uint64_t(n_out) * 16 : 0);
+    const unsigned long long hs[8] = {h[0], h[1], 0, h[4], h[3], 0, 0, 0};
+    c.timing.hop(6, final, 0.0, hs, 0.0, kb);
+    c.timing.name_last_hop("nbg::k_rev_pull", "", final ? "nbg::k_bits_compact<1, 8, 1>" : nullptr);
+    return n_out;
+  }
+  void hop_rev_pull() {
+    rev_pull(false, nullptr);
+    const unsigned long long* h = K.h + kCntUpto;
+    std::swap(bitsA, bitsB);
+    have_list = false;
+    list_n = int64_t(h[2]);  // the kept rows are the new bitmap's population
+    off_ready = false;
+    E = E_known = int64_t(h[1]);
+    nset_global = multi ? int64_t(K.h[kCntGlobal]) : int64_t(h[0]);
+    Eg = multi ? int64_t(K.h[kCntGlobal + 1]) : E;
   }
 
   // the frontier list and its degree scan as the expansion's arguments
@@ -3682,7 +3973,7 @@ struct GoQuery {
     // bitmap is slice-relative, ensure_list's input is the bottom-up's global-indexed one
     const bool lazy = bu_ok && !multi_root && c.opt("compact_list", 0) == 0;
     launch_compact(c, map, lo, n_own, row_ptr, row_ok, 1, lazy ? nullptr : F, reinterpret_cast<uint16_t*>(bitsA),
-                   K.d, es.odeg.as<uint32_t>(), false, 1, 0, -1, nullptr, map_bound);
+                   K.d, D.deg, false, 1, 0, -1, nullptr, map_bound);
     piggy_used = multi && lazy && spec_ok && c.opt("comm_piggy", 1) != 0;
     if (multi && !piggy_used) dev_allsum(c, K.d, {kCntSet, kCntDegSum}, K.d + kCntGlobal);
     if (lazy)
@@ -3736,6 +4027,9 @@ struct GoQuery {
       hvids = std::move(spec_hvids);
       nrows = int64_t(fin_h[kSpecRows]);
       record_bu_hop(fin_h, fin_L, true, nrows);
+    } else if (bu && rev) {
+      vids.alloc(size_t(c.n_global + 64) * 8);
+      nrows = rev_pull(true, vids.p);
     } else if (bu) {
       FastArgs tfp = fp;
       if (pk == PK_FAST) tfp.data = es.tr.props[size_t(fpk.col)].data.p;
@@ -4019,7 +4313,7 @@ struct GoQuery {
   // U = starts + everything reached within N - 1 hops (with out-edges), so a visited-pruned BFS
   // builds U expanding each vertex once (levels B_k) and ONE final step runs over U.
   int32_t upto_distinct() {
-    if (!es.odeg.p) throw Error(NBG_E_STATE, "GO UPTO: the snapshot has no out-degree array");
+    if (!D.deg) throw Error(NBG_E_STATE, "GO UPTO: the snapshot has no out-degree array");
     const size_t bm = size_t(map_bytes(c) / 8 + 64);
     c.ws_vis.ensure(2 * bm);
     auto* vis = c.ws_vis.as<unsigned long long>();
@@ -4029,13 +4323,13 @@ struct GoQuery {
     const size_t wb = size_t((n_own + 63) / 64) * 8;
     NBG_HIP(hipMemcpyAsync(vis, bitsA, wb, hipMemcpyDeviceToDevice, c.stream));
     NBG_HIP(hipMemcpyAsync(uni, bitsA, wb, hipMemcpyDeviceToDevice, c.stream));
-    const uint32_t* odeg = es.odeg.as<uint32_t>();
+    const uint32_t* odeg = D.deg;  // (REVERSELY: in-degrees)
     unsigned long long* const S = K.d + kCntUpto;
     // one lane a row, at most upto_grid blocks adding their sums into ks shards (RMAT-26, UPTO 3
     // query: 1024 blocks 0.985 ms, 2048 / 4096 / 8192 0.799, 16384 0.925; 4096 unsharded 0.842)
     const int grid = grid_cap((n_own + 63) / 64 * 64, 256, int(std::max<int64_t>(1, c.opt("upto_grid", 4096))));
     // a level's successor is certainly expanded top-down: the claim writes it as a list too
-    const bool td_certain = !bu_ok || bu_force < 0;
+    const bool td_certain = rev || !bu_ok || bu_force < 0;  // (REVERSELY: never k_upto_bu, which reads es.tr)
     const int64_t n_scan = std::min<int64_t>(n_own, es.bu_in_tiles * 128);  // rows with an in-edge lie below
     int64_t bn = nF;                     // |B_k| on this rank
     int64_t un = nF, ue = E, ueg = Eg;   // |U|, outdeg(U) on this rank, outdeg(U) over ranks
@@ -4200,9 +4494,12 @@ int32_t go_run(Ctx& c, const nbg_go_spec& s, nbg_rows* out) {
   if (!c.finalized) throw Error(NBG_E_STATE, "snapshot not finalized");
   if (s.steps < 1) throw Error(NBG_E_INVALID_ARG, "steps must be >= 1");
   if (s.upto != 0 && s.upto != 1) throw Error(NBG_E_INVALID_ARG, "upto must be 0 or 1");
-  if (s.edge_type <= 0) throw Error(NBG_E_INVALID_ARG, "GO ... REVERSELY is not supported (GoExecutor.cpp:203-205)");
-  auto it = c.edges.find(s.edge_type);
+  // edge_type < 0: GO ... OVER -edge_type REVERSELY, the convention of nbg_get_bound
+  if (s.edge_type == 0 || s.edge_type == INT32_MIN) throw Error(NBG_E_INVALID_ARG, "edge_type must not be 0");
+  auto it = c.edges.find(s.edge_type < 0 ? -s.edge_type : s.edge_type);
   if (it == c.edges.end()) throw Error(NBG_E_INVALID_ARG, "edge type not in snapshot");
+  if (s.edge_type < 0 && !it->second.in.row_ptr.p)
+    throw Error(NBG_E_UNSUPPORTED, "GO ... REVERSELY: the edge type has no in CSR");
   c.timing = Timing{};
   timing_reset(c);
   // per-hop event pairs (hop stats); bench.py's timed loop turns them off like a production

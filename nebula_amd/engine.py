@@ -308,7 +308,8 @@ class GraphSpace:
         t = _lib.Timing()
         self._check(self.L.nbg_last_timing(self.h, C.byref(t)))
         d = {k: getattr(t, k) for k, _ in t._fields_ if k not in ("hops", "n_hops")}
-        modes = {0: "top-down", 1: "bottom-up", 2: "sp-expand", 3: "sp-probe", 4: "sp-sweep", 5: "sp-walk"}
+        modes = {0: "top-down", 1: "bottom-up", 2: "sp-expand", 3: "sp-probe", 4: "sp-sweep", 5: "sp-walk",
+                 6: "rev-pull"}
         d["hops"] = [{"mode": modes.get(h.mode, h.mode), "mode_id": h.mode, "final": bool(h.final_hop), "ms": h.ms,
                       "bytes": int(h.bytes), "c": list(h.c), "kernel_ms": h.kernel_ms,
                       "kernel_bytes": int(h.kernel_bytes),
@@ -390,12 +391,19 @@ class GraphSpace:
         return names, types, cols, offs, keep
 
     def go(self, starts, steps: int, edge_type: int, where=None, yields: Iterable = (), distinct: bool = False,
-           keep_on_device: bool = False, inputs=None, upto: bool = False, order_by=None) -> RowSet:
-        """GO ... FROM starts. `inputs`: the piped / variable rows ($-.prop / $var.prop), one per start,
+           keep_on_device: bool = False, inputs=None, upto: bool = False, order_by=None,
+           reversely: bool = False) -> RowSet:
+        """GO ... FROM starts. `reversely`: GO ... OVER edge REVERSELY, the in-edges of the frontier
+        (sent as -edge_type; a negative `edge_type` passed directly means the same, both at once is a
+        ValueError).  `inputs`: the piped / variable rows ($-.prop / $var.prop), one per start,
         as [(name, NBG_T_*, values)] (GoExecutor::getPropFromInterim).  `upto`: GO UPTO `steps` STEPS,
         the rows of GO 1 .. `steps` STEPS together (include/nebula_amd.h).  `order_by`:
         [(column index, desc)] -- GO ... | ORDER BY: the result stays in HBM, nbg_order_by orders it
         there, and `keep_on_device` applies to the ordered table."""
+        if reversely:
+            if edge_type < 0:
+                raise ValueError("reversely=True with a negative edge_type: give the edge type itself")
+            edge_type = -edge_type
         starts = np.ascontiguousarray(starts, dtype=np.int64)
         want_device = keep_on_device
         if order_by is not None:
@@ -862,18 +870,19 @@ class AddVerticesProcessor(_WriteProcessor):
 
 
 class GoExecutor:
-    """GO [[UPTO] N STEPS] FROM starts OVER edge [WHERE f] [YIELD [DISTINCT] cols]."""
+    """GO [[UPTO] N STEPS] FROM starts OVER edge [REVERSELY] [WHERE f] [YIELD [DISTINCT] cols]."""
 
     def __init__(self, space: GraphSpace, starts, edge_type: int, steps: int = 1, where=None, yields=(),
-                 distinct: bool = False, upto: bool = False, order_by=None):
+                 distinct: bool = False, upto: bool = False, order_by=None, reversely: bool = False):
         self.space, self.starts, self.edge_type = space, starts, edge_type
         self.steps, self.where, self.yields, self.distinct = steps, where, list(yields), distinct
         self.upto = upto
+        self.reversely = reversely  # OVER edge REVERSELY (GoExecutor::prepareOver's reversely_)
         self.order_by = order_by  # [(column index, desc)]: ... | ORDER BY, ordered on the device
 
     def execute(self, keep_on_device: bool = False) -> RowSet:
         return self.space.go(self.starts, self.steps, self.edge_type, self.where, self.yields, self.distinct,
-                             keep_on_device, upto=self.upto, order_by=self.order_by)
+                             keep_on_device, upto=self.upto, order_by=self.order_by, reversely=self.reversely)
 
 
 ASC, DESC = 0, 1  # OrderFactor::OrderType (src/parser/TraverseSentences.h)
