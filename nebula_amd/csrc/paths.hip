@@ -3114,6 +3114,11 @@ struct DevBatch {
     W.dv_chx.alloc(size_t(cap_ch) * 4);
     W.dv_slot.alloc(size_t(cap_ch) * 8);
     W.dv_wchx.alloc(size_t(cap_wch) * 4);
+    // the chunk table starts defined: after an overflow k_dv_expand still reads the slot of every
+    // reserved chunk (the probe's claims), those of an X entry that did not fit and nobody filled
+    // included, and follows a set slot through chx into X
+    NBG_HIP(hipMemsetAsync(W.dv_chx.p, 0, W.dv_chx.bytes, c.stream));
+    NBG_HIP(hipMemsetAsync(W.dv_slot.p, 0xff, W.dv_slot.bytes, c.stream));
     CarveSize pair_bytes;
     SpDev sized{};
     dv_pair_layout(pair_bytes, dvB, sized);

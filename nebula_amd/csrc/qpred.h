@@ -2,7 +2,7 @@
 // packed bottom-up words (host and device).
 //
 // A packed word is (bucket << gbits) | src gidx, the bucket that of the packed column's value:
-//   q_bucket     value -> bucket, floor((v - min) * 2^bits / range)              (snapshot.hip)
+//   q_bucket     value -> bucket, floor((v - min) * 2^bits / range)             (csr_build.hip)
 //   make_qargs_core (min, range, bits, gbits, op, k) -> QArgs: which buckets the compare decides
 //   q_test       word -> 1 pass / 0 fail / -1 undecided        (k_bu_lean, k_bu_rest_lean, k_expand)
 //   fin_args     QArgs -> FinArgs: the same decisions as unsigned word ranges           (k_bu_fin)

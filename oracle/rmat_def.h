@@ -1,7 +1,7 @@
 // oracle/rmat_def.h -- TEST INFRASTRUCTURE ONLY (see refcpu.h).
 // The synthetic RMAT definition shared by the oracle's two restatements (refcpu.cpp: the KV
 // store + processors; rmat_graph.cpp: the index-space CSR used at the configured sizes).  The
-// product generator (nebula_amd/csrc/snapshot.hip) restates the same arithmetic on the device.
+// product generator (nebula_amd/csrc/build_common.h) restates the same arithmetic on the device.
 #pragma once
 #include <cstdint>
 

@@ -1,4 +1,4 @@
-"""Streamed RMAT build (snapshot.hip finalize_rmat_stream): the one-rank builder for graphs past
+"""Streamed RMAT build (rmat_stream.hip finalize_rmat_stream): the one-rank builder for graphs past
 the tuple stage's 2^32 cap (BASELINE.json configs[4], RMAT-28).  It regenerates the samples per
 src-gidx bucket instead of staging them, so it must give the staged build's snapshot exactly:
 same vertex numbering, same rows in the same (RocksDB key) order, same weights.
