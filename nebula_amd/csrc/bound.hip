@@ -7,7 +7,7 @@
 //   * collectEdgeProps' firstLoop (QueryBaseProcessor.inl:349-402): on multi-version data the
 //     older version a filter lets through ahead of a row's ordinary rows.
 //
-// The filter runs through the GO expansion (expand_flags, traverse.hip): a flag byte per edge slot
+// The filter runs through the GO expansion (expand_flags, expand.hip): a flag byte per edge slot
 // of the request's flattened adjacency; a select turns the flags into the kept rows.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>

@@ -1,6 +1,6 @@
 // edge_lookup.h -- the 16-lane group lookup of one (rank, dst) key in a CSR row: a binary search
 // under the row's bytewise order down to a window, then a coalesced scan of the window.  Shared by
-// k_fetch_edge (fetch.hip: FETCH PROP ON an edge type) and k_mirror_check (traverse.hip: do the in
+// k_fetch_edge (fetch.hip: FETCH PROP ON an edge type) and k_mirror_check (go_variants.hip: do the in
 // keys mirror the out keys, GO ... REVERSELY).
 #pragma once
 #include <hip/hip_runtime.h>

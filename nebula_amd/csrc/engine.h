@@ -676,28 +676,30 @@ void snapshot_write_part(Ctx& c, int32_t part, const uint8_t* kb, const uint64_t
                          const uint8_t* vb, const uint64_t* voff, size_t n);
 void snapshot_commit(Ctx& c);
 void lookup_gidx(Ctx& c, const int64_t* d_vids, int32_t* d_gidx, int64_t n);
+// counters.hip
 // the device counters d[0, n) (n <= 256) into pinned host h[0, n) once every launch before has
-// finished on the context's stream (a one-block publish kernel + a host spin, traverse.hip)
+// finished on the context's stream (a one-block publish kernel + a host spin)
 // `before` (optional): an event recorded just ahead of the publish kernel
 // shards > 1: d is a sharded counter block (word i = sum of d[i + s * kShardStride], s < shards)
 void fetch_counters(Ctx& c, const unsigned long long* d, int n, unsigned long long* h, hipEvent_t before = nullptr,
                     int shards = 1);
-// sharded block sums (traverse.hip block_add_sums): shard s of counter word i at i + s * kShardStride
+// sharded block sums (go_device.h block_add_sums): shard s of counter word i at i + s * kShardStride
 constexpr size_t kShardStride = 256;
 constexpr int kSumShards = 8;
 // one host wait (counted in Timing::host_waits) until the device publishes `seq` in `word`
 void wait_host_word(Ctx& c, const unsigned long long* word, uint64_t seq);
 // a query's total_ms (ev[0] -> ev[1]) once asked for (go_run records ev[1] without waiting)
 void resolve_total(Ctx& c);
-// traverse.hip
-int32_t go_run(Ctx& c, const nbg_go_spec& spec, nbg_rows* out);
-// the in keys' derived data of a REVERSELY query, EdgeSpace::rev (collective: every rank calls it
-// at the same point)
-void ensure_rev(Ctx& c, EdgeSpace& es);
-// the out CSR replica and its out-degrees (collective: every rank calls it at the same point)
-void ensure_rep_out(Ctx& c, EdgeSpace& es);
 void timing_reset(Ctx& c);
 void timing_resolve(Ctx& c);
+// traverse.hip
+int32_t go_run(Ctx& c, const nbg_go_spec& spec, nbg_rows* out);
+// go_variants.hip: the in keys' derived data of a REVERSELY query, EdgeSpace::rev (collective:
+// every rank calls it at the same point)
+void ensure_rev(Ctx& c, EdgeSpace& es);
+// paths.hip: the out CSR replica and its out-degrees (collective: every rank calls it at the
+// same point)
+void ensure_rep_out(Ctx& c, EdgeSpace& es);
 // bound.hip
 int32_t get_bound_run(Ctx& c, int32_t et, const int32_t* parts, const int64_t* vids, size_t n,
                       const uint8_t* filter, size_t flen, const nbg_prop_def* cols, size_t ncols,

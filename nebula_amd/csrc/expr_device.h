@@ -1,6 +1,7 @@
 // expr_device.h -- the device expression VM: the value model, the column loads and the postfix
 // evaluator of a compiled Program (program.h), plus the typed-compare fast path.  Shared by the
-// query translation units (traverse.hip, bound.hip); everything here is inlined into their kernels.
+// query translation units (expand.hip, yield.hip, bound.hip); everything here is inlined into
+// their kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -12,7 +12,7 @@
 //                     under the row's bytewise order down to a window, then a coalesced scan of the
 //                     window's col segment (short rows: the scan alone)
 //   select            the kept (row, edge) pairs in key order (rocprim::select)
-//   yield_rows        traverse.hip's YIELD materialiser over those pairs
+//   yield_rows        yield.hip's YIELD materialiser over those pairs
 // DISTINCT deduplicates the keys, then the rows, with nbg_set_op's hash machinery (setops.hip).
 #include <hip/hip_runtime.h>
 

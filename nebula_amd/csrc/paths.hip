@@ -3423,7 +3423,7 @@ struct HostBatch {
     bf.sweep_next = sweep_next ? sweep_next->as<uint64_t>() : nullptr;
     bf.cap_sweep = sweep_next ? cap_sweep_next : 0;
   }
-  // the counters on the host (publish kernel + spin, traverse.hip: a memcpy + stream sync
+  // the counters on the host (publish kernel + spin, counters.hip: a memcpy + stream sync
   // round trip cost ~20 us per call, ~15 calls per batch)
   void sync_counters() { fetch_counters(c, cnt, C_N, hc); }
   void zero(uint32_t mask, int64_t* xdeg = nullptr) { k_cnt_zero<<<1, 64, 0, c.stream>>>(cnt, mask, xdeg); }

@@ -1,5 +1,6 @@
 // query_common.h -- host-side helpers the .hip translation units share: grid sizing, the rocprim
-// scan / select wrappers, and the entry points of traverse.hip's expansion that bound.hip calls.
+// scan / select wrappers, and the entry points of the expansion (expand.hip) and the YIELD
+// materialiser (yield.hip) that bound.hip and fetch.hip call.
 #pragma once
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
@@ -78,18 +79,21 @@ struct ExpandArgs {
   int32_t* root_next;
 };
 
-// ---- defined in traverse.hip ----
+// ---- defined in expand.hip ----
 EvalEnv make_env(Ctx& c, EdgeSpace& es, Csr& csr, int32_t etype);  // builds the column tables on first use
 FastArgs fast_args(const Csr& csr, const FastPred& fpk);
 uint64_t expand_bytes(int64_t nF, int64_t E, int pred_width, int mode);
-int32_t column_result_type(int32_t t);
 // the EXP_FLAGS expansion: a.flags[slot] = the edge at that slot passes the predicate
 void expand_flags(Ctx& c, ExpandArgs a, int pk, const FastArgs& fp, const Program* dprog, const EvalEnv& env, int64_t E);
+
+// ---- defined in yield.hip ----
+// the type a stored column is returned as: FLOAT widens to DOUBLE, VID and TIMESTAMP are INTs
+int32_t column_result_type(int32_t t);
 // the YIELD materialiser (k_materialize, k_str_pack) over n rows (rows_src[i] + lo = the row's src
 // gidx, rows_edge[i] = its edge in env's CSR; rows_edge == nullptr: vertex rows, whose programs hold
 // only P_SRCTAG and constants).  out: one column per program, STRING columns as packed bytes + n + 1
 // offsets, ready for hand_out_rows.  An evaluation error on any row throws NBG_E_EVAL (err_what).
-constexpr int kMaxYieldCols = 16;  // YieldArgs::cols (traverse.hip kMaxYields)
+constexpr int kMaxYieldCols = 16;  // YieldArgs::cols (go_launch.h kMaxYields)
 struct YieldOut {
   std::vector<int32_t> types;  // NBG_T_*
   std::vector<DevBuf> dev, off;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Count memory instruction kinds per kernel in a hipcc -S device assembly file.
 
-    hipcc ... --offload-device-only -S csrc/traverse.hip -o /tmp/tr.s; python tools/asm_loads.py /tmp/tr.s k_bu_quad"""
+    hipcc ... --offload-device-only -S csrc/bottom_up.hip -o /tmp/bu.s; python tools/asm_loads.py /tmp/bu.s k_bu_lean"""
 import re
 import sys
 

@@ -1,5 +1,5 @@
 // atomic_tail.hip -- what the block-sum tail of a resident grid costs: every block of a grid adds
-// K per-block sums into device counters at its end (block_add_sums in traverse.hip).  Variants:
+// K per-block sums into device counters at its end (block_add_sums in go_device.h).  Variants:
 //   dense : the K counters of one hop on one 128-byte line (the engine's layout)
 //   spread: each counter on a line of its own
 //   shard : spread, and blocks add into one of S shards (blockIdx % S), S lines apart
