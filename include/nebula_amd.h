@@ -471,6 +471,74 @@ int32_t nbg_fetch_edges(nbg_ctx* ctx, int32_t edge_type, const int64_t* src, con
                         const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields,
                         int32_t distinct, int32_t keep_on_device, nbg_rows* out);
 
+/* ---- FIND props FROM tag / edge WHERE (FindSentence) ----------------------------------------
+ * FIND prop_list FROM name_label where_clause: the reference parses the sentence (parser.yy:565-571,
+ * FindSentence, src/parser/TraverseSentences.h:83-113) and FindExecutor::prepare answers "Does not
+ * support" (src/graph/FindExecutor.cpp:20-22).  The semantics below are this build's (DESIGN.md
+ * section 5, divergence 12): a scan of the resident columns that returns the vertices / edges whose
+ * props satisfy WHERE, the start vids of a later GO.
+ * Vertices: the candidates are every vid with a row of tag_id in the vid's own part that this rank
+ * owns, vertices no edge names included; of several versions of the row the bytewise-first is read:
+ * the row nbg_fetch_vertices returns for that vid.  Column 0 is the vid (NBG_T_VID, "VertexID");
+ * the yields follow.
+ * Edges: the candidates are every entry of the edge_type out-CSR in a row nbg_go would expand (the
+ * keys sit in src's own part), each the bytewise-first version of its (src, rank, dst) group.
+ * Columns 0..2 are _src, _dst, _rank (NBG_T_VID); the yields follow.  A negative edge_type is
+ * NBG_E_UNSUPPORTED (in-edges carry no props), a type not in the snapshot NBG_E_INVALID_ARG.
+ * A candidate is selected when WHERE is true; where_len = 0 selects every candidate, and a WHERE
+ * without any prop node is legal.  A WHERE whose value is not a bool counts as nbg_go counts it
+ * (asBool: int != 0, double != 0.0, a string iff empty).
+ * WHERE and yields: Expression::encode bytes, compiled under FETCH PROP ON's rule.  Vertices: the
+ * legal prop node is alias.prop with alias = the tag's name (another alias: NBG_E_INVALID_ARG).
+ * Edges: alias.prop with any alias, and the key props _src, _dst, _rank; _type is
+ * NBG_E_UNSUPPORTED.  A $^ / $$ / $- / $var node or an edge-key function (_src(e), ...) is
+ * NBG_E_INVALID_ARG ("Only support form of alias.prop in fetch sentence."); an unknown prop is
+ * NBG_E_IMPROPER_DATA_TYPE.  Arithmetic, relational, logical and unary operators and constants
+ * over these nodes run on the device VM as in nbg_go (graphd semantics, not storage's).
+ * n_yields = 0 returns the key columns alone (the form a pipe into GO wants; not FETCH's "every
+ * field", not an error).  More than 15 yields (vertices) / 13 yields (edges): NBG_E_UNSUPPORTED
+ * (a result has at most 16 columns).
+ * Evaluation: a WHERE evaluation error on any candidate (a field its row lacks included) fails the
+ * call with NBG_E_EVAL, as does a YIELD evaluation error on any selected row.  What is no
+ * candidate is never evaluated and cannot fail the call: a row of a foreign part, a vid of another
+ * rank.
+ * Row order: deterministic, otherwise unspecified: ascending by position in the scanned structure
+ * (edges: out-CSR entry order; vertices: column index order, vertices without edges last), the
+ * same on every run and for every value of the option below.  Chain nbg_order_by for a meaningful
+ * order.
+ * out: column types as for nbg_fetch_*; in HBM when keep_on_device = 1, else on the host; STRING
+ * columns as packed bytes + n_rows + 1 offsets.  A device result feeds nbg_order_by, nbg_set_op
+ * and nbg_fetch_* (keys_on_device) in place; nbg_go takes host starts, so FIND | GO copies column 0
+ * to the host.
+ * Errors: NBG_E_STATE before finalize; NBG_E_TAG_PROP_NOT_FOUND unknown tag_id; NBG_E_INVALID_ARG
+ * null pointers with lengths > 0, keep_on_device outside {0, 1}; NBG_E_UNSUPPORTED 2^32 selected
+ * rows or more.
+ * world_size > 1: every rank scans what it owns and emits those rows; no collective is issued.
+ * After nbg_snapshot_commit the scan reads the new commit.
+ * nbg_last_timing then reports total_ms, launches, host_waits and n_hops = 0; expand_ms,
+ * expand_launches and expand_bytes describe the scan kernels alone (edges);
+ * edges_scanned: the entries of the out-CSR the edge scan went over, 0 for vertices.
+ * host_waits: 3 with selected rows (the match count together with the WHERE error count, the
+ * materialiser's error count together with its STRING byte totals, the hand-out), 2 without
+ * (no materialiser; nbg_find_vertices with n_yields = 0 has none either), 1 when there is nothing
+ * to scan (no entry of the type / no row of the tag).
+ * launches, edges with a typed compare (below): 3 (count, scan of the tile counts, emit; 2 without
+ * selected rows), plus 1 on the first such call on a type after finalize / a commit (the table of
+ * each tile's first row).  Edges otherwise: 4 (frontier, tile rows, expansion, select), plus 1 with
+ * selected rows (slot -> entry), plus 2 when foreign-part rows exist (visible degrees, their scan).
+ * Vertices: 2 (flags, select), plus 1 with selected rows (the vid column).  All: plus the
+ * materialiser's with selected rows and yields: 1, and 2 per STRING column (1 if all are empty).
+ * Engine option "find_fast" (tests, measurement): the edge scan of a WHERE of the form
+ * `int prop REL int constant` reads the prop's column alone, 8 entries per lane in 8- / 16-byte
+ * loads (k_find_count / k_find_emit); every other WHERE runs nbg_go's expansion kernel over all
+ * rows.  0 forces the latter for every WHERE, 1 or unset takes the former wherever eligible.     */
+int32_t nbg_find_vertices(nbg_ctx* ctx, int32_t tag_id, const uint8_t* where, size_t where_len,
+                          const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields,
+                          int32_t keep_on_device, nbg_rows* out);
+int32_t nbg_find_edges(nbg_ctx* ctx, int32_t edge_type, const uint8_t* where, size_t where_len,
+                       const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields,
+                       int32_t keep_on_device, nbg_rows* out);
+
 /* ---- timing of the last call (HIP events on the engine stream) --------------------------- */
 /* one hop of the last nbg_go: mode 0 = top-down expansion of a frontier list, 1 = bottom-up
  * over the transposed CSR.  c[]: top-down {frontier, entries, next frontier, 0, 0, 0};

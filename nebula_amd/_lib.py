@@ -34,7 +34,8 @@ EXPORTS = [
     "nbg_snapshot_gen_rmat", "nbg_snapshot_finalize", "nbg_snapshot_write_part", "nbg_snapshot_commit",
     "nbg_snapshot_info_get",
     "nbg_snapshot_out_degree", "nbg_rows_free", "nbg_get_bound", "nbg_bound_stats", "nbg_go", "nbg_shortest_path",
-    "nbg_order_by", "nbg_set_op", "nbg_fetch_vertices", "nbg_fetch_edges", "nbg_last_timing", "nbg_set_option",
+    "nbg_order_by", "nbg_set_op", "nbg_fetch_vertices", "nbg_fetch_edges", "nbg_find_vertices", "nbg_find_edges",
+    "nbg_last_timing", "nbg_set_option",
 ]
 
 
@@ -141,6 +142,8 @@ def load(path: str | os.PathLike | None = None):
         "nbg_fetch_vertices": (i32, [vp, i32, vp, sz, i32, C.POINTER(vp), C.POINTER(sz), sz, i32, i32, C.POINTER(Rows)]),
         "nbg_fetch_edges": (i32, [vp, i32, vp, vp, vp, sz, i32, C.POINTER(vp), C.POINTER(sz), sz, i32, i32,
                                   C.POINTER(Rows)]),
+        "nbg_find_vertices": (i32, [vp, i32, vp, sz, C.POINTER(vp), C.POINTER(sz), sz, i32, C.POINTER(Rows)]),
+        "nbg_find_edges": (i32, [vp, i32, vp, sz, C.POINTER(vp), C.POINTER(sz), sz, i32, C.POINTER(Rows)]),
         "nbg_last_timing": (i32, [vp, C.POINTER(Timing)]),
         "nbg_set_option": (i32, [vp, C.c_char_p, i64]),
     }

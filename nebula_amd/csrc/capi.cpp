@@ -406,6 +406,34 @@ int32_t nbg_fetch_edges(nbg_ctx* ctx, int32_t edge_type, const int64_t* src, con
   });
 }
 
+int32_t nbg_find_vertices(nbg_ctx* ctx, int32_t tag_id, const uint8_t* where, size_t where_len,
+                          const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields, int32_t keep_on_device,
+                          nbg_rows* out) {
+  return guarded(ctx, [&](Ctx& c) {
+    if (!out || (where_len && !where) || (n_yields && (!yields || !yield_lens)))
+      throw Error(NBG_E_INVALID_ARG, "bad arguments");
+    memset(out, 0, sizeof(*out));
+    const int32_t rc =
+        nbg::find_vertices_run(c, tag_id, where, where_len, yields, yield_lens, n_yields, keep_on_device, out);
+    nbg::timing_resolve(c);
+    return rc;
+  });
+}
+
+int32_t nbg_find_edges(nbg_ctx* ctx, int32_t edge_type, const uint8_t* where, size_t where_len,
+                       const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields, int32_t keep_on_device,
+                       nbg_rows* out) {
+  return guarded(ctx, [&](Ctx& c) {
+    if (!out || (where_len && !where) || (n_yields && (!yields || !yield_lens)))
+      throw Error(NBG_E_INVALID_ARG, "bad arguments");
+    memset(out, 0, sizeof(*out));
+    const int32_t rc =
+        nbg::find_edges_run(c, edge_type, where, where_len, yields, yield_lens, n_yields, keep_on_device, out);
+    nbg::timing_resolve(c);
+    return rc;
+  });
+}
+
 int32_t nbg_last_timing(nbg_ctx* ctx, nbg_timing* out) {
   return guarded(ctx, [&](Ctx& c) {
     if (!out) throw Error(NBG_E_INVALID_ARG, "null out");

@@ -579,6 +579,15 @@ struct Ctx {
   // coherent pinned host block of the device-driven batches: publish slots, the pairs, results
   void* sp_host = nullptr;
   size_t sp_host_bytes = 0;
+  // FIND over an edge type (find.hip): the row holding the first entry of every 2048-entry tile of
+  // the out CSR the last fast scan read, rebuilt when that CSR changed (kept across calls;
+  // allocated outside the query pool)
+  struct FindWork {
+    DevBuf tile_row;  // int32 [tiles + 2]
+    int32_t type = 0;
+    const void* row_ptr = nullptr;
+    int64_t n_rows = -1, nnz = -1, commits = -1;
+  } find;
   Timing timing;
   hipEvent_t ev[8] = {};
   DevBuf ws_tile_rows;  // k_expand: frontier entry of each tile's first slot
@@ -720,6 +729,11 @@ int32_t fetch_vertices_run(Ctx& c, int32_t tag_id, const int64_t* vids, size_t n
 int32_t fetch_edges_run(Ctx& c, int32_t edge_type, const int64_t* src, const int64_t* dst, const int64_t* rank, size_t n,
                         int32_t keys_on_device, const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields,
                         int32_t distinct, int32_t keep_on_device, nbg_rows* out);
+// find.hip
+int32_t find_vertices_run(Ctx& c, int32_t tag_id, const uint8_t* where, size_t where_len, const uint8_t* const* yields,
+                          const size_t* yield_lens, size_t n_yields, int32_t keep_on_device, nbg_rows* out);
+int32_t find_edges_run(Ctx& c, int32_t edge_type, const uint8_t* where, size_t where_len, const uint8_t* const* yields,
+                       const size_t* yield_lens, size_t n_yields, int32_t keep_on_device, nbg_rows* out);
 // comm.cpp
 void comm_alltoallv_bytes(Ctx& c, const void* send, const size_t* send_bytes, const size_t* send_off,
                           void* recv, const size_t* recv_bytes, const size_t* recv_off);

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 
+#include "call_common.h"
 #include "device_common.h"
 #include "edge_lookup.h"
 #include "engine.h"
@@ -193,15 +194,6 @@ std::vector<Program> compile_yields(Ctx& c, const uint8_t* const* yields, const 
   return progs;
 }
 
-void begin_call(Ctx& c) {
-  c.timing = Timing{};
-  timing_reset(c);
-  c.total_pending = false;
-  if (c.host_stage_used) NBG_HIP(hipStreamSynchronize(c.stream));  // a failed query's copies
-  c.host_stage_used = 0;
-  NBG_HIP(hipEventRecord(c.ev[0], c.stream));
-}
-
 // rows -> DISTINCT by value (uniqResult) -> the caller
 void finish_call(Ctx& c, YieldOut& y, int64_t n_rows, bool distinct, bool keep_on_device, nbg_rows* out) {
   const size_t ncols = y.types.size();
@@ -222,13 +214,7 @@ void finish_call(Ctx& c, YieldOut& y, int64_t n_rows, bool distinct, bool keep_o
       n_rows = kept;
     }
   }
-  NBG_HIP(hipEventRecord(c.ev[1], c.stream));
-  c.total_pending = true;
-  auto h = std::make_unique<HostRows>();
-  h->types = y.types;
-  h->dev = std::move(y.dev);
-  hand_out_rows(c, std::move(h), y.off, y.str_bytes, n_rows, keep_on_device, out);
-  out->edges_scanned = c.timing.edges_scanned;
+  hand_out_call(c, y, n_rows, keep_on_device, out);
 }
 
 // the kept entries of `in` (flag != 0) in order behind `out`; the last select's count lands in cnt
@@ -360,17 +346,6 @@ int32_t fetch_edges_impl(Ctx& c, EdgeSpace& es, const int64_t* src, const int64_
              "fetch_edges: YIELD evaluation failed", y);
   finish_call(c, y, n_rows, distinct, keep_on_device, out);
   return NBG_OK;
-}
-
-template <typename F>
-int32_t run_guarded(Ctx& c, F f) {
-  try {
-    return f();
-  } catch (...) {
-    // no launch or copy may still use a block this call frees on the way out
-    (void)hipStreamSynchronize(c.stream);
-    throw;
-  }
 }
 
 }  // namespace

@@ -14,6 +14,8 @@
                            ``FETCH PROP ON edge src->dst@rank``, also piped from a result table: a device
                            point lookup of every key (src/graph/FetchVerticesExecutor.cpp,
                            FetchEdgesExecutor.cpp).
+* ``FindExecutor``      -- ``FIND props FROM tag / edge WHERE ...``: a device scan of the resident
+                           columns (the reference parses the sentence and does not run it).
 * ``FindPathExecutor``  -- FIND SHORTEST PATH FROM ... TO ... OVER ... UPTO N STEPS (the
                            reference's FindExecutor is a stub, src/graph/FindExecutor.cpp:20-22;
                            semantics in include/nebula_amd.h), batched bidirectional BFS.
@@ -613,6 +615,28 @@ class GraphSpace:
                                            C.byref(out)))
         return RowSet(out, holder=_RowsHandle(self.L, out))
 
+    def _find(self, fn, type_id: int, where, yields, keep_on_device: bool) -> RowSet:
+        wb = X.encode(where) if where is not None else b""
+        wbuf = C.create_string_buffer(wb, len(wb) + 1)
+        yp, yl, ny, _bufs = self._yield_views(yields)
+        out = _lib.Rows()
+        self._check(fn(self.h, int(type_id), C.cast(wbuf, C.c_void_p) if wb else None, len(wb), yp, yl, ny,
+                       int(bool(keep_on_device)), C.byref(out)))
+        return RowSet(out, holder=_RowsHandle(self.L, out))
+
+    def find_vertices(self, tag: int, where=None, yields: Iterable = (), keep_on_device: bool = False) -> RowSet:
+        """FIND props FROM tag WHERE ... (nbg_find_vertices): every vertex with a row of tag id `tag`
+        for which `where` (a tag.prop expression; None: every such vertex) is true.  Column 0 is the
+        vid, the `yields` follow; rows come in the tag's column order (deterministic; chain order_by
+        for a meaningful one)."""
+        return self._find(self.L.nbg_find_vertices, tag, where, yields, keep_on_device)
+
+    def find_edges(self, edge_type: int, where=None, yields: Iterable = (), keep_on_device: bool = False) -> RowSet:
+        """FIND props FROM edge WHERE ... (nbg_find_edges): every out-edge of `edge_type` for which
+        `where` (over edge.prop, _src, _dst, _rank; None: every edge) is true.  Columns 0..2 are
+        _src, _dst, _rank, the `yields` follow; rows come in out-CSR entry order."""
+        return self._find(self.L.nbg_find_edges, edge_type, where, yields, keep_on_device)
+
     def shortest_path(self, src, dst, edge_type: int, max_steps: int = 5) -> "PathResult":
         """Pairwise shortest paths (src[i] -> dst[i]) over edge_type out-edges."""
         src = np.ascontiguousarray(src, dtype=np.int64)
@@ -974,6 +998,28 @@ class FetchEdgesExecutor:
             src, dst, *rest = keys_or_rowset
             rank = rest[0] if rest else None
         return self.space.fetch_edges(self.edge_type, src, dst, rank, self.yields, self.distinct, keep_on_device)
+
+
+class FindExecutor:
+    """FIND props FROM type_name WHERE ... (FindSentence(type, props) + WHERE,
+    src/parser/TraverseSentences.h:83-113; the reference's FindExecutor::prepare answers "Does not
+    support").  `type_name` resolves through the registered tag and edge names; `props`: the
+    sentence's prop list, yielded as type_name.prop behind the key columns (the vid; _src, _dst,
+    _rank).  Its usual use pipes column 0 into a GO: GoExecutor(...).execute(rs.columns[0])."""
+
+    def __init__(self, space: GraphSpace, type_name: str, props=(), where=None):
+        is_tag, is_edge = type_name in space.tag_ids, type_name in space.edge_types
+        if is_tag and is_edge:
+            raise ValueError(f"{type_name!r} names a tag and an edge")
+        if not (is_tag or is_edge):
+            raise ValueError(f"{type_name!r} is neither a registered tag nor a registered edge")
+        self.space, self.is_tag, self.where = space, is_tag, where
+        self.type_id = space.tag_ids[type_name] if is_tag else space.edge_types[type_name]
+        self.yields = [X.AliasProp(type_name, p) for p in props]
+
+    def execute(self, keep_on_device: bool = False) -> RowSet:
+        find = self.space.find_vertices if self.is_tag else self.space.find_edges
+        return find(self.type_id, self.where, self.yields, keep_on_device)
 
 
 class FindPathExecutor:
