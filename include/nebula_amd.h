@@ -405,6 +405,76 @@ int32_t nbg_order_by(nbg_ctx* ctx, const nbg_rows* in, const int32_t* cols, cons
 int32_t nbg_set_op(nbg_ctx* ctx, int32_t op, const nbg_rows* left, const nbg_rows* right,
                    int32_t distinct, int32_t keep_on_device, nbg_rows* out);
 
+/* ---- GROUP BY ----------------------------------------------------------------------------------
+ * `... | GROUP BY $-.a YIELD $-.a, COUNT(*), SUM($-.b)` on a result table.  The reference
+ * (v1.0.0-beta) has no GROUP BY; the later nGQL releases do, and the semantics below are owned by
+ * this build (DESIGN.md divergence 13).  in: a plain row table as nbg_go / nbg_order_by /
+ * nbg_set_op hand it out, host-resident (uploaded) or device-resident on this context (read in
+ * place); it is neither consumed nor modified, and the caller frees both in and out.  A table
+ * carrying row_vertex, vertices, failed parts or paths is NBG_E_INVALID_ARG.
+ * Output columns: the n_keys key columns first, in key_cols order and with their input types (a
+ * key column may repeat: the repeat decides nothing and is output again), then the n_aggs
+ * aggregates: agg_fns[i] over column agg_cols[i].
+ *   NBG_AGG_COUNT   the group's row count, NBG_T_INT; agg_cols[i] is ignored (-1 included)
+ *   NBG_AGG_SUM     over VID / INT / TIMESTAMP the int64 sum with two's-complement wrap-around,
+ *                   NBG_T_INT; over DOUBLE an IEEE sum of the group's values, NBG_T_DOUBLE, whose
+ *                   association order is fixed by the input alone: the same input gives the same
+ *                   bits on every run, but it is not defined to equal a left-to-right sum
+ *   NBG_AGG_AVG     NBG_T_DOUBLE: double(that wrapped sum) / double(count) over integers (the
+ *                   `sum / count` of nbg_bound_stats), that double sum / count over DOUBLE
+ *   NBG_AGG_MIN / NBG_AGG_MAX   the column's own type, under ORDER BY's order: integers as signed
+ *                   int64, false < true, doubles numerically with NaN after +inf.  For doubles
+ *                   the value is canonical: a zero extreme is +0.0, a NaN extreme is the quiet NaN
+ *                   0x7ff8000000000000, every other value keeps its own bits
+ * SUM / AVG over BOOL or STRING is NBG_E_IMPROPER_DATA_TYPE (validOperation, as nbg_bound_stats);
+ * MIN / MAX over STRING is NBG_E_UNSUPPORTED (STRING key columns are fully supported).
+ * Groups: one output row per distinct key tuple under nbg_set_op's row equality (integers and bools
+ * by value, strings as bytes plus length with embedded NUL bytes legal, -0.0 == +0.0, every NaN
+ * equals every NaN).  The key columns of an output row carry the bits of the group's first input
+ * row, and the groups come in first-occurrence order (the order UNION DISTINCT leaves;
+ * deterministic; chain nbg_order_by for another one).  n_keys = 0 puts every row into one group
+ * (`| YIELD COUNT(*), SUM($-.x)`); n_aggs = 0 with keys is a DISTINCT projection of the key
+ * columns; both zero is NBG_E_INVALID_ARG.  Zero input rows give zero output rows with the
+ * output's column count and types, for n_keys = 0 too (there is no NULL to put into MIN).
+ * NBG_E_INVALID_ARG: a null ctx, in or out; a null array with a count > 0; a column index out of
+ * range; a function outside 1..5; keep_on_device outside {0, 1}.
+ * NBG_E_UNSUPPORTED: n_keys + n_aggs > 16 (a result has at most 16 columns); 2^32 rows or more.
+ * NBG_E_NOMEM: the workspace did not fit; the input is untouched.  Besides the output and a host
+ * table's upload, with keys: per row 8 B (hash), 16 to 32 B (the table: 8 B x the power of two
+ * >= 2 x rows), 4 B (group id), 1 B + 4 B (first-occurrence byte and its scan); per group 4 B (first
+ * row).  The aggregates add, on the atomic path, per group 8 B x (1 + the aggregates other than
+ * COUNT); on the ordered path per row 8 B (the order: two row indices) and up to 16 B (radix keys),
+ * per group 12 B (segment offsets, chunk numbers) and 8 B per aggregate for every 16384 rows of a
+ * group of more than 4096.
+ * out: in HBM when keep_on_device = 1, else on the host (STRING columns as packed bytes + n_rows+1
+ * offsets).  edges_scanned is copied from in.
+ * Works on any context (no snapshot needed).  Rank-local: with world_size > 1 each rank groups the
+ * rows it holds and no collective is issued; INTEGRATION.md has the rule by which a caller merges
+ * the ranks' partial tables.
+ * Two paths, the same table from both wherever both are defined.  Atomic (no SUM / AVG over
+ * DOUBLE): 64-bit integer atomics per row, through LDS first when the groups are few.  Ordered (a
+ * SUM / AVG over DOUBLE, or engine option "group_sorted" = 1): the rows in a stable order by group,
+ * each segment reduced in a tree fixed by its length; no float atomics anywhere.
+ * nbg_last_timing then reports total_ms (uploads and kernels; the copies to the host behind them
+ * are not in it), launches (kernels; a scan counts as one), host_waits and n_hops = 0.
+ * host_waits, independent of the row and group counts: 1 (the hand-out) for zero input rows or
+ * n_keys = 0; with keys and rows 2 (the fetch of the group count, and the hand-out) on the atomic
+ * path and for n_aggs = 0, 3 on the ordered path (one more for the order's digit histogram) unless
+ * there is one group only (2); plus one per STRING column of a device-resident input with rows
+ * (its byte total).
+ * Engine options (tests, measurement): "group_sorted" (default 0), "group_lds_max" (default 1024:
+ * the atomic path accumulates in LDS when the group count is at most this and groups x (1 +
+ * aggregates other than COUNT) <= 4096 words), "set_hash_bits" (masks the key hash as in
+ * nbg_set_op).  No option changes a result.                                                     */
+#define NBG_AGG_SUM 1    /* cpp2::StatType values, as nbg_bound_stats takes them */
+#define NBG_AGG_COUNT 2
+#define NBG_AGG_AVG 3
+#define NBG_AGG_MIN 4
+#define NBG_AGG_MAX 5
+int32_t nbg_group_by(nbg_ctx* ctx, const nbg_rows* in, const int32_t* key_cols, size_t n_keys,
+                     const int32_t* agg_fns, const int32_t* agg_cols, size_t n_aggs,
+                     int32_t keep_on_device, nbg_rows* out);
+
 /* ---- FETCH PROP ON (FetchVerticesExecutor / FetchEdgesExecutor) ---------------------------
  * FETCH PROP ON tag vid, ... [YIELD [DISTINCT] ...] and FETCH PROP ON edge src->dst[@rank], ...:
  * the device replacement of FetchVerticesExecutor::fetchVertices / processResult

@@ -8,10 +8,11 @@ from . import expr  # noqa: F401
 from ._lib import NbgError, load  # noqa: F401
 from .engine import (AVG, COUNT, SUM, AddEdgesProcessor, AddEdgesRequest, AddVerticesProcessor,  # noqa: F401
                      AddVerticesRequest, Edge, EdgeKey, ExecResponse, Tag, Vertex, FetchEdgesExecutor, FetchVerticesExecutor, FindExecutor, FindPathExecutor, GetNeighborsRequest, GoExecutor,  # noqa: F401
-                     GraphSpace, OrderByExecutor, PathResult, PropDef, QueryBoundProcessor, QueryResponse, QueryStatsProcessor,
+                     GraphSpace, GroupByExecutor, OrderByExecutor, PathResult, PropDef, QueryBoundProcessor, QueryResponse, QueryStatsProcessor,
                      QueryStatsResponse, RowSet, SetExecutor, pack_kv)
 
 __all__ = ["GraphSpace", "QueryBoundProcessor", "QueryStatsProcessor", "GoExecutor", "FindPathExecutor", "OrderByExecutor", "SetExecutor",
+           "GroupByExecutor",
            "FetchVerticesExecutor", "FetchEdgesExecutor", "FindExecutor",
            "PathResult", "GetNeighborsRequest", "PropDef", "QueryResponse", "QueryStatsResponse", "RowSet",
            "NbgError", "expr", "load", "pack_kv", "SUM", "COUNT", "AVG", "AddEdgesProcessor", "AddEdgesRequest",

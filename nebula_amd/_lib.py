@@ -24,6 +24,7 @@ T_BOOL, T_INT, T_VID, T_FLOAT, T_DOUBLE, T_STRING, T_TIMESTAMP = 1, 2, 3, 4, 5, 
 OWNER_SOURCE, OWNER_DEST, OWNER_EDGE = 1, 2, 3
 ABI_VERSION = 7  # NBG_ABI_VERSION of include/nebula_amd.h
 SET_UNION, SET_INTERSECT, SET_MINUS = 1, 2, 3  # NBG_SET_* (nbg_set_op)
+AGG_SUM, AGG_COUNT, AGG_AVG, AGG_MIN, AGG_MAX = 1, 2, 3, 4, 5  # NBG_AGG_* (nbg_group_by)
 
 # every symbol the header declares (tests/test_capi.py checks the .so exports them all)
 EXPORTS = [
@@ -34,7 +35,7 @@ EXPORTS = [
     "nbg_snapshot_gen_rmat", "nbg_snapshot_finalize", "nbg_snapshot_write_part", "nbg_snapshot_commit",
     "nbg_snapshot_info_get",
     "nbg_snapshot_out_degree", "nbg_rows_free", "nbg_get_bound", "nbg_bound_stats", "nbg_go", "nbg_shortest_path",
-    "nbg_order_by", "nbg_set_op", "nbg_fetch_vertices", "nbg_fetch_edges", "nbg_find_vertices", "nbg_find_edges",
+    "nbg_order_by", "nbg_set_op", "nbg_group_by", "nbg_fetch_vertices", "nbg_fetch_edges", "nbg_find_vertices", "nbg_find_edges",
     "nbg_last_timing", "nbg_set_option",
 ]
 
@@ -139,6 +140,7 @@ def load(path: str | os.PathLike | None = None):
         "nbg_shortest_path": (i32, [vp, i32, vp, vp, sz, i32, C.POINTER(Rows)]),
         "nbg_order_by": (i32, [vp, C.POINTER(Rows), vp, vp, sz, i32, C.POINTER(Rows)]),
         "nbg_set_op": (i32, [vp, i32, C.POINTER(Rows), C.POINTER(Rows), i32, i32, C.POINTER(Rows)]),
+        "nbg_group_by": (i32, [vp, C.POINTER(Rows), vp, sz, vp, vp, sz, i32, C.POINTER(Rows)]),
         "nbg_fetch_vertices": (i32, [vp, i32, vp, sz, i32, C.POINTER(vp), C.POINTER(sz), sz, i32, i32, C.POINTER(Rows)]),
         "nbg_fetch_edges": (i32, [vp, i32, vp, vp, vp, sz, i32, C.POINTER(vp), C.POINTER(sz), sz, i32, i32,
                                   C.POINTER(Rows)]),

@@ -379,6 +379,18 @@ int32_t nbg_set_op(nbg_ctx* ctx, int32_t op, const nbg_rows* left, const nbg_row
   });
 }
 
+int32_t nbg_group_by(nbg_ctx* ctx, const nbg_rows* in, const int32_t* key_cols, size_t n_keys, const int32_t* agg_fns,
+                     const int32_t* agg_cols, size_t n_aggs, int32_t keep_on_device, nbg_rows* out) {
+  return guarded(ctx, [&](Ctx& c) {
+    if (!in || !out || in == out || (n_keys && !key_cols) || (n_aggs && (!agg_fns || !agg_cols)))
+      throw Error(NBG_E_INVALID_ARG, "bad arguments");
+    memset(out, 0, sizeof(*out));
+    const int32_t rc = nbg::group_by_run(c, *in, key_cols, n_keys, agg_fns, agg_cols, n_aggs, keep_on_device, out);
+    nbg::timing_resolve(c);
+    return rc;
+  });
+}
+
 int32_t nbg_fetch_vertices(nbg_ctx* ctx, int32_t tag_id, const int64_t* vids, size_t n, int32_t keys_on_device,
                            const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields, int32_t distinct,
                            int32_t keep_on_device, nbg_rows* out) {

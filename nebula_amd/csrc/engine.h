@@ -722,6 +722,9 @@ int32_t order_by_run(Ctx& c, const nbg_rows& in, const int32_t* cols, const int3
 // setops.hip
 int32_t set_op_run(Ctx& c, int32_t op, const nbg_rows& left, const nbg_rows& right, int32_t distinct,
                    int32_t keep_on_device, nbg_rows* out);
+// group.hip
+int32_t group_by_run(Ctx& c, const nbg_rows& in, const int32_t* key_cols, size_t n_keys, const int32_t* agg_fns,
+                     const int32_t* agg_cols, size_t n_aggs, int32_t keep_on_device, nbg_rows* out);
 // fetch.hip
 int32_t fetch_vertices_run(Ctx& c, int32_t tag_id, const int64_t* vids, size_t n, int32_t keys_on_device,
                            const uint8_t* const* yields, const size_t* yield_lens, size_t n_yields, int32_t distinct,

@@ -35,7 +35,7 @@ constexpr int kHistRounds = 4;
 constexpr int64_t kSmallTileRows = int64_t(1) << 18;  // up to here 1024-row tiles, 4096 above
 constexpr int64_t kMaxStrFactorLen = 256;
 
-enum KeyKind : int32_t { KK_ENCODED = 0, KK_INT, KK_DOUBLE, KK_BOOL, KK_STRLEN, KK_STRCHUNK };
+enum KeyKind : int32_t { KK_ENCODED = 0, KK_INT, KK_DOUBLE, KK_BOOL, KK_STRLEN, KK_STRCHUNK, KK_U32 };
 
 // where element i's key comes from: encoded keys (KK_ENCODED), or a column read through the
 // current index (idx == nullptr: row i) and encoded on the fly
@@ -56,6 +56,7 @@ __device__ __forceinline__ uint64_t load_key(const KeySrc& s, int64_t i) {
     case KK_DOUBLE: k = okey::enc_double(static_cast<const double*>(s.data)[r]); break;
     case KK_BOOL: k = okey::enc_bool(static_cast<const uint8_t*>(s.data)[r]); break;
     case KK_STRLEN: k = okey::enc_str_len(s.off[r + 1] - s.off[r]); break;
+    case KK_U32: k = static_cast<const uint32_t*>(s.data)[r]; break;  // GROUP BY's group ids
     default:
       k = okey::enc_str_chunk(static_cast<const uint8_t*>(s.data) + s.off[r], s.off[r + 1] - s.off[r], s.chunk);
   }
@@ -437,6 +438,17 @@ int32_t order_by_impl(Ctx& c, const nbg_rows& in, const std::vector<std::pair<in
 }
 
 }  // namespace
+
+// GROUP BY's ordered path (group.hip): the rows in a stable order by their 32-bit group id, with
+// the sort above (one key, so one host wait; the digits no id differs in are skipped).  Returns
+// false when no pass ran: every id is the same and the input order is the answer.
+bool order_rows_by_u32(Ctx& c, const uint32_t* keys, int64_t n, DevBuf& idx) {
+  OrderSort srt(c, n);
+  srt.sort_key(KeySrc{keys, nullptr, nullptr, KK_U32, 0, 0}, true);
+  if (!srt.idx) return false;
+  idx = std::move(srt.idxs[srt.idx_next ^ 1]);  // the buffer the last pass wrote
+  return true;
+}
 
 int32_t order_by_run(Ctx& c, const nbg_rows& in, const int32_t* fcols, const int32_t* fdesc, size_t n_factors,
                      int32_t keep_on_device, nbg_rows* out) {

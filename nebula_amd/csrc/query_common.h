@@ -115,4 +115,9 @@ struct TableCol {
 // (one host wait)
 int64_t distinct_first_rows(Ctx& c, const std::vector<TableCol>& cols, int64_t n, DevBuf& idx);
 
+// ---- defined in order.hip ----
+// idx = the row numbers [0, n) in a stable ascending order of keys[row] (ORDER BY's radix sort,
+// one host wait); false, and idx untouched, when every key is the same.  n > 0
+bool order_rows_by_u32(Ctx& c, const uint32_t* keys, int64_t n, DevBuf& idx);
+
 }  // namespace nbg

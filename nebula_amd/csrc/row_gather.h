@@ -1,5 +1,5 @@
-// row_gather.h -- the row-table plumbing nbg_order_by and nbg_set_op share (included by order.hip
-// and setops.hip; every definition is translation-unit local):
+// row_gather.h -- the row-table plumbing nbg_order_by, nbg_set_op and nbg_group_by share (included
+// by order.hip, setops.hip and group.hip; every definition is translation-unit local):
 //   check_plain_table  the argument checks of a plain row table
 //   upload_table       a host table's columns to HBM (a device table is read in place)
 //   gather_rows        output columns = input columns permuted / selected by a uint32 row index

@@ -556,6 +556,28 @@ class GraphSpace:
                                       int(bool(keep_on_device)), C.byref(out)))
         return RowSet(out, holder=_RowsHandle(self.L, out), raw_strings=lraw or rraw)
 
+    def group_by(self, table, keys, aggs, keep_on_device: bool = False) -> RowSet:
+        """GROUP BY on a result table (nbg_group_by).  `table`: what order_by takes, on the host or
+        kept in HBM; it is not changed.  `keys`: column indices; `aggs`: [(fn, col)] with fn one of
+        _lib.AGG_* or "COUNT" / "SUM" / "AVG" / "MIN" / "MAX", col None for COUNT.  The output has
+        the key columns, then one column per aggregate, one row per distinct key tuple in
+        first-occurrence order (no keys: one row over the whole table)."""
+        keys = [int(k) for k in keys]
+        fns, cols = [], []
+        for fn, col in aggs:
+            fns.append(agg_function(fn))
+            cols.append(-1 if col is None else int(col))
+        rows, _keep, raw = self._table_rows(table, "group_by")
+        if isinstance(table, RowSet) and not table.on_device:
+            rows.edges_scanned = table.edges_scanned  # (a device table's rows carry theirs)
+        kc = (C.c_int32 * max(len(keys), 1))(*keys)
+        af = (C.c_int32 * max(len(fns), 1))(*fns)
+        ac = (C.c_int32 * max(len(cols), 1))(*cols)
+        out = _lib.Rows()
+        self._check(self.L.nbg_group_by(self.h, C.byref(rows), C.cast(kc, C.c_void_p), len(keys), C.cast(af, C.c_void_p),
+                                        C.cast(ac, C.c_void_p), len(fns), int(bool(keep_on_device)), C.byref(out)))
+        return RowSet(out, holder=_RowsHandle(self.L, out), raw_strings=raw)
+
     @staticmethod
     def _fetch_key(key, who: str):
         """One key argument of a fetch call -> (pointer, n, on_device, keepalive): an array, or
@@ -957,6 +979,52 @@ class SetExecutor:
             rs = self.space.set_op(self.op, left, right, True, keep_on_device=True)
             return self.space.order_by(rs, [(c, ASC) for c in range(len(rs.types))], keep_on_device)
         return self.space.set_op(self.op, left, right, self.distinct, keep_on_device)
+
+
+AGG_FUNCTIONS = {"SUM": _lib.AGG_SUM, "COUNT": _lib.AGG_COUNT, "AVG": _lib.AGG_AVG, "MIN": _lib.AGG_MIN,
+                 "MAX": _lib.AGG_MAX}
+
+
+def agg_function(fn) -> int:
+    """An aggregate function as nbg_group_by takes it: an _lib.AGG_* constant, or its name in any
+    letter case."""
+    if isinstance(fn, str):
+        if fn.upper() not in AGG_FUNCTIONS:
+            raise ValueError(f"aggregate function {fn!r}")
+        return AGG_FUNCTIONS[fn.upper()]
+    if int(fn) not in AGG_FUNCTIONS.values():
+        raise ValueError(f"aggregate function {fn!r}")
+    return int(fn)
+
+
+class GroupByExecutor:
+    """... | GROUP BY $-.a, ... YIELD $-.a, COUNT(*), SUM($-.b), ...  (no counterpart in the reference:
+    DESIGN.md divergence 13).  `keys`: names written `$-.name` or `name`; `aggs`: [(fn, name)] with
+    fn "COUNT" / "SUM" / "AVG" / "MIN" / "MAX" in any letter case or an _lib.AGG_* constant, name
+    None or "*" for COUNT; `columns`: the input's column names (the YIELD aliases).  An unknown
+    function or name raises ValueError: a group key cannot be dropped silently the way ORDER BY
+    drops a factor.  The output's columns are the keys, then the aggregates.  `space` may be None
+    for resolution alone."""
+
+    def __init__(self, space, keys, aggs, columns):
+        self.space, self.columns = space, list(columns)
+        self.key_cols = [self._resolve(name) for name in keys]
+        self.aggs = []  # [(AGG_*, column index or None)], as GraphSpace.group_by takes them
+        for fn, name in aggs:
+            fn = agg_function(fn)
+            if fn == _lib.AGG_COUNT and name in (None, "*"):
+                self.aggs.append((fn, None))
+            else:
+                self.aggs.append((fn, self._resolve(name)))
+
+    def _resolve(self, name) -> int:
+        field = name[3:] if isinstance(name, str) and name.startswith("$-.") else name
+        if field not in self.columns:
+            raise ValueError(f"group by: the input has no column {name!r}")
+        return self.columns.index(field)
+
+    def execute(self, rowset, keep_on_device: bool = False) -> RowSet:
+        return self.space.group_by(rowset, self.key_cols, self.aggs, keep_on_device)
 
 
 class FetchVerticesExecutor:
