@@ -194,13 +194,21 @@ __device__ inline void bu_rest_scan(const bool (&pend)[R], bool (&found)[R], con
 //    first (almost none: hub-first slot 0 is nearly always in a dense frontier), and only the
 //    tiles below es.bu_both_tiles (the last row with an in- and an out-edge: one rank numbers
 //    such vertices first, snapshot k_class_key); the tiles past it get zero words;
+//  * a non-final hop reads its tile's shape word (EdgeSpace::tile_shape, option bu_lean_shape)
+//    through a scalar load one tile ahead: a two-slot tile (no row has a third entry) leaves no
+//    row pending, so the second half is never entered for it, and a uniform tile (every row that
+//    can be found has the same out-degree) loads no per-row degree and adds degree x found rows
+//    to the sum -- wave-uniform run-time branches, mixed and wide tiles run as before
+//    (DESIGN.md section 6);
 //  * the final hop (PK_FAST) decides each slot by two scalar compares of its packed bucket
 //    (QArgs); a frontier hit in an undecided bucket and rows with more than 4 entries are left
 //    pending for k_bu_rest_lean (rest_from 0).  A predicate on a column that is not the packed
 //    one makes every bucket undecided: the first pass then only clears rows with no frontier
 //    in-neighbour among their slots, and the rest pass reads the values.
 // Outputs: next-frontier and pending words; partials [0] found, [1] their out-degree sum,
-// [2] slab words read, [3] pending rows.
+// [2] slab words read, [3] pending rows.  STATS with tile_stats (bu_probe_stats 2 / 3): [6] / [7]
+// count a non-final hop's work tiles by shape (1: two-slot / uniform, 2: both / neither) instead
+// of the probes.
 // HUB: the block keeps the first cw words of the bitmap (the highest-out-degree vertices) in LDS
 // and answers candidates there from it; the global probe of such a slot is out of bounds.
 // Partials [6] / [7]: candidate probes sent to L2 / answered from LDS.
@@ -213,7 +221,8 @@ __global__ __launch_bounds__(1024, 8) void k_bu_lean(const uint2* __restrict__ l
                                                      const uint32_t* __restrict__ odeg, QArgs q_arg,
                                                      unsigned long long* __restrict__ partials, int cw,
                                                      const uint8_t* __restrict__ odeg8,
-                                                     unsigned long long* gate, GateIn gi, int atomic_sums) {
+                                                     unsigned long long* gate, GateIn gi, int atomic_sums,
+                                                     const uint32_t* __restrict__ shape, int tile_stats) {
   if (!gate_open(gi, gate)) return;  // a speculative hop that the direction choice did not take
   __shared__ unsigned long long lds[kSlots * 16];
   extern __shared__ uint32_t s_fb[];  // [0, cw): the bitmap's hub words; [cw]: a zero word
@@ -232,6 +241,17 @@ __global__ __launch_bounds__(1024, 8) void k_bu_lean(const uint2* __restrict__ l
   uint32_t nglob = 0, nhub = 0;
   unsigned long long nfound = 0, npend = 0, nwords = 0;  // wave-uniform
   unsigned long long odsum = 0;
+  unsigned long long odsum_u = 0;  // wave-uniform: the found rows of uniform tiles, degree x count
+  // Non-final hops: the tile's shape word (EdgeSpace::tile_shape; shape == nullptr: every tile
+  // wide and mixed, the code below as it was), a wave-uniform index, so a scalar load; past the
+  // work tiles it reads the word of tile work_tiles, at most the array's padding.
+  auto shape_index = [&](int64_t t) -> uint32_t {
+    return __builtin_amdgcn_readfirstlane(uint32_t(min(t, work_tiles)));
+  };
+  auto shape_word = [&](uint32_t i) -> uint32_t { return FINAL || !shape ? kShapeWide | kShapeMixed : shape[i]; };
+  uint32_t shn[U];  // asked for one iteration ahead
+#pragma unroll
+  for (int u = 0; u < U; u++) shn[u] = shape_word(shape_index(wave * U + u));
   // One slot word: its probe (global byte offset, out of bounds unless an L2 candidate; LDS
   // index, cw -- the zero word -- unless a hub candidate) and, final hop, its bucket's answer
   // (bit k of `pm` pass, of `um` undecided).  A failing bucket is no candidate; an undecided
@@ -249,7 +269,7 @@ __global__ __launch_bounds__(1024, 8) void k_bu_lean(const uint2* __restrict__ l
     const bool hub = HUB && wi < ucw;
     goff = cand && !hub ? wi * 4u : 0xfffffff0u;
     lidx = cand && hub ? wi : ucw;
-    if (STATS) {  // (diagnostic instantiation: the counters' masks cost the hot loop registers)
+    if (STATS && !tile_stats) {  // (diagnostic instantiation: the counters' masks cost the hot loop registers)
       nglob += cand && !hub;
       nhub += cand && hub;
     }
@@ -261,6 +281,26 @@ __global__ __launch_bounds__(1024, 8) void k_bu_lean(const uint2* __restrict__ l
     uint2 a[U][2], b[U][2];
     uint32_t od[U][2];
     bool v[U];
+    // this iteration's shape words are taken first, then the next iteration's are asked for,
+    // ahead of the tiles' work: the wait is then for loads issued an iteration ago (k_bu_fin's
+    // form; with the loads above it every tile waited a scalar round trip).  The empty asm ties
+    // the next load's index to this iteration's word in its register: the compiler otherwise
+    // sinks the word's first use, and with it the wait, below the new load.
+    bool two[U], uni[U];  // wave-uniform: no row has a third entry / every row has out-degree ud
+    uint32_t ud[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      uint32_t cur = shn[u];
+      if (!FINAL) {
+        uint32_t ni = shape_index(t0 + nwaves * U + u);
+        asm volatile("" : "+s"(cur), "+s"(ni));
+        __builtin_amdgcn_sched_barrier(0);
+        shn[u] = shape_word(ni);
+      }
+      two[u] = (cur & kShapeWide) == 0u;
+      ud[u] = cur & kShapeMixed;
+      uni[u] = ud[u] != kShapeMixed;
+    }
 #pragma unroll
     for (int u = 0; u < U; u++) {
       v[u] = t0 + u < work_tiles;
@@ -275,11 +315,14 @@ __global__ __launch_bounds__(1024, 8) void k_bu_lean(const uint2* __restrict__ l
             b[u][h] = make_uint2(uint32_t(y), uint32_t(y >> 32));
           }
           // 1 B per row; 255 stands for a larger degree, read from odeg where a row is found
-          od[u][h] = FINAL ? 1u : uint32_t(__builtin_nontemporal_load(odeg8 + r + 64 * h));
+          // (a uniform tile: the degree is in its shape word, no load)
+          od[u][h] = FINAL ? 1u : ud[u];
+          if (!FINAL && !uni[u]) od[u][h] = uint32_t(__builtin_nontemporal_load(odeg8 + r + 64 * h));
         } else {
           a[u][h] = lo[r + 64 * h];
           if (FINAL) b[u][h] = hi[r + 64 * h];
-          od[u][h] = FINAL ? 1u : odeg[r + 64 * h];
+          od[u][h] = FINAL ? 1u : ud[u];
+          if (!FINAL && !uni[u]) od[u][h] = odeg[r + 64 * h];
         }
       }
     }
@@ -364,8 +407,9 @@ __global__ __launch_bounds__(1024, 8) void k_bu_lean(const uint2* __restrict__ l
           pend[u][h] = v[u] && !f[u][h] && (b[u][h].y != 0xffffffffu || (hm & um[u][h]) != 0u);
         } else {
           f[u][h] = hm != 0u && od[u][h] > 0;
-          // rows with a third slot to test: live, not found, slot 1 present
-          pend[u][h] = v[u] && hm == 0u && od[u][h] > 0 && a[u][h].y != 0xffffffffu;
+          // rows with a third slot to test: live, not found, slot 1 present -- none in a
+          // two-slot tile (no row of it has a third entry: its pending words are zero)
+          pend[u][h] = v[u] && !two[u] && hm == 0u && od[u][h] > 0 && a[u][h].y != 0xffffffffu;
         }
       }
       nwords += v[u] ? (FINAL ? 8u : 4u) * 64u : 0u;  // every lane's two rows
@@ -449,11 +493,21 @@ __global__ __launch_bounds__(1024, 8) void k_bu_lean(const uint2* __restrict__ l
       nfound += uint64_t(__popcll(f0) + __popcll(f1));
       npend += uint64_t(__popcll(p0) + __popcll(p1));
       if (!FINAL) {
+        if (uni[u]) {  // wave-uniform
+          odsum_u += uint64_t(ud[u]) * uint64_t(__popcll(f0) + __popcll(f1));
+        } else {
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
-          uint32_t d = f[u][h] ? od[u][h] : 0u;
-          if (NT && d == 255u) d = odeg[row_of(t, h)];  // odeg8 saturates at 255
-          odsum += uint64_t(d);
+          for (int h = 0; h < 2; h++) {
+            uint32_t d = f[u][h] ? od[u][h] : 0u;
+            if (NT && d == 255u) d = odeg[row_of(t, h)];  // odeg8 saturates at 255
+            odsum += uint64_t(d);
+          }
+        }
+        if (STATS && tile_stats) {  // (diagnostic) the tiles by shape instead of the probes
+          const bool c6 = tile_stats == 2 ? two[u] && uni[u] : two[u];
+          const bool c7 = tile_stats == 2 ? !two[u] && !uni[u] : uni[u];
+          nglob += lane == 0 && c6;
+          nhub += lane == 0 && c7;
         }
       }
     }
@@ -466,6 +520,7 @@ __global__ __launch_bounds__(1024, 8) void k_bu_lean(const uint2* __restrict__ l
     }
   // wave-uniform counters enter the block sums once, from lane 0
   if (lane != 0) nfound = npend = nwords = 0;
+  if (lane == 0) odsum += odsum_u;
   unsigned long long acc64[8] = {nfound, odsum, nwords, npend, 0, 0, nglob, nhub};
   if (atomic_sums) block_add_sums(acc64, 8, lds, partials, atomic_sums);
   else block_store_partials(acc64, 8, lds, partials);
@@ -1159,13 +1214,23 @@ void bu_first_pass(Ctx& c, const EdgeSpace& es, const BuPlan& p, const uint32_t*
   if (sel == kHub && (p.fast || es.odeg8.p)) sel = kHubNt;
   const Named<Fn>& k = lean[p.pk][sel];
   if (p.shm > 48 * 1024) lds_limit(reinterpret_cast<const void*>(k.fn), p.shm);
+  // the shape words of a non-final hop (they describe es.odeg); bu_lean_shape = 0 (A/B runs,
+  // tests): every tile runs as wide and mixed.  bu_probe_stats 2 / 3: the counting instantiations
+  // count tiles by shape in [6] / [7]: two-slot / uniform, or both / neither
+  const uint32_t* shape = !p.fast && odeg == es.odeg.as<uint32_t>() && c.opt("bu_lean_shape", 1) != 0
+                              ? es.tile_shape.as<uint32_t>()
+                              : nullptr;
   k.fn<<<p.grid, p.bs, p.shm, c.stream>>>(lo, hi, p.ntiles, p.work, fb, p.fb_bytes, o.nb, o.pbits,
                                           p.fast ? nullptr : odeg, p.q, o.partials, cw, es.odeg8.as<uint8_t>(), o.gate,
-                                          gi, p.atomic_sums);
+                                          gi, p.atomic_sums, shape, p.probe_stats > 1 ? p.probe_stats - 1 : 0);
   L.k0 = k.name;
   // the non-final first pass reads one out-degree per row of its work tiles: 1 B (odeg8, the
-  // non-temporal instantiations) or 4 B (odeg)
-  if (!p.fast) L.od_bytes = uint64_t(p.work) * 128u * (sel == kHubNt ? 1u : 4u);
+  // non-temporal instantiations) or 4 B (odeg); with the shape words 4 B per work tile and the
+  // degrees of the mixed tiles only
+  if (!p.fast) {
+    const uint64_t od_tiles = shape ? uint64_t(p.work - std::min(p.work, es.shape_tiles[0])) : uint64_t(p.work);
+    L.od_bytes = od_tiles * 128u * (sel == kHubNt ? 1u : 4u) + (shape ? uint64_t(p.work) * 4u : 0u);
+  }
 }
 
 // The rest pass over the rows the first pass left pending.  Fills L.k1 and rest_rec.
@@ -1241,7 +1306,8 @@ BuLaunch launch_bu_lean(Ctx& c, EdgeSpace& es, const uint32_t* fb, uint32_t* nbi
 
 // byte models of a bottom-up hop's two passes from their counters.
 // First pass: 4 B per slab word read, the frontier bitmap once, the next-frontier and pending
-// bits written, the out-degrees a non-final hop read (od_bytes: 1 B per work row from odeg8;
+// bits written, the out-degrees a non-final hop read (od_bytes: 1 B per work row from odeg8 --
+// with the shape words 4 B per work tile and the bytes of the mixed tiles only;
 // rounds 2-4 counted 4 B for every row, 1.5x the bytes the default kernel reads) or the
 // tile_wide bits the final hop read (one per work tile; the slab words already count 4 a row
 // for a two-slot tile).  Rest pass:

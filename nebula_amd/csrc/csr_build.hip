@@ -740,6 +740,52 @@ __global__ void k_tile_wide(const int64_t* trp, int64_t n, uint32_t* wide) {
   }
 }
 
+// EdgeSpace::tile_shape: one word per 128-row tile, a wave per tile (a lane owns rows l and l + 64,
+// as in the first pass).  Bit 31: the tile_wide bit.  Bits 0-30: the out-degree that every row of
+// the tile with an in-edge has, or kShapeMixed when they differ (or no row has one, or the degree
+// does not fit below it).  Rows without an in-edge do not count: the pass can never find them, so
+// it never uses their degree -- the rows past the last vertex (the owned range is padded to 64)
+// and a run of out-edge-only rows behind the last live one are such rows.
+__global__ void k_tile_shape(const int64_t* trp, const uint32_t* odeg, int64_t n, int64_t ntiles, uint32_t* shape) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (blockIdx.x * int64_t(blockDim.x) + threadIdx.x) >> 6;
+  const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
+  for (int64_t t = wave; t < ntiles; t += nwaves) {
+    bool wide = false, has[2];
+    uint32_t o[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int64_t d = t * 128 + lane + 64 * h;
+      const int64_t ind = d < n ? trp[d + 1] - trp[d] : 0;
+      wide = wide || ind >= 3;
+      has[h] = ind > 0;
+      o[h] = has[h] ? odeg[d] : 0u;
+    }
+    // the degree of the tile's first row with an in-edge; none: mixed
+    const unsigned long long b0 = __ballot(has[0]), b1 = __ballot(has[1]);
+    uint32_t d0 = kShapeMixed;
+    if (b0) d0 = uint32_t(__shfl(int(o[0]), __ffsll((long long)b0) - 1));
+    else if (b1) d0 = uint32_t(__shfl(int(o[1]), __ffsll((long long)b1) - 1));
+    const bool mixed = (has[0] && o[0] != d0) || (has[1] && o[1] != d0);
+    const bool w = __ballot(wide) != 0ull, m = __ballot(mixed) != 0ull || d0 >= kShapeMixed;
+    if (lane == 0) shape[t] = (w ? kShapeWide : 0u) | (m ? kShapeMixed : d0);
+  }
+}
+// out[0] uniform tiles, out[1] two-slot tiles, out[2] tiles that are both, out[3] uniform tiles of
+// out-degree 0, among the first nt tiles
+__global__ void k_shape_count(const uint32_t* shape, int64_t nt, unsigned long long* out) {
+  unsigned long long a[4] = {0, 0, 0, 0};
+  for (int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; t < nt; t += int64_t(gridDim.x) * blockDim.x) {
+    const uint32_t s = shape[t];
+    const bool uni = (s & kShapeMixed) != kShapeMixed, two = !(s & kShapeWide);
+    a[0] += uni, a[1] += two, a[2] += uni && two, a[3] += (s & kShapeMixed) == 0u;
+  }
+  for (int k = 0; k < 4; k++) {
+    for (int o = 32; o > 0; o >>= 1) a[k] += (unsigned long long)__shfl_xor((long long)a[k], o);
+    if ((threadIdx.x & 63) == 0 && a[k]) atomicAdd(out + k, a[k]);
+  }
+}
+
 // rest records (EdgeSpace::brec): row d's start and clamped in-degree, then its first
 // kRecEntries entries of src, as one 64-byte line (four 16-byte stores)
 __global__ void k_build_rec(const int64_t* trp, const int32_t* src, int64_t n, uint4* rec) {
@@ -1017,6 +1063,29 @@ struct TransposeBuild {
     NBG_HIP(hipMemsetAsync(es.tile_wide.p, 0, size_t(nt / 32 + 2) * 4, c.stream));
     if (n_own)
       k_tile_wide<<<grid_for(n_own), 256, 0, c.stream>>>(t.row_ptr.as<int64_t>(), n_own, es.tile_wide.as<uint32_t>());
+    // the non-final first pass's word per tile (wide bit + common out-degree), two words of
+    // padding (wide, mixed): k_bu_lean reads its next tile's word ahead
+    es.tile_shape.alloc(size_t(nt + 2) * 4);
+    NBG_HIP(hipMemsetAsync(es.tile_shape.p, 0xff, size_t(nt + 2) * 4, c.stream));
+    if (n_own)
+      k_tile_shape<<<grid_for(nt * 64), 256, 0, c.stream>>>(t.row_ptr.as<int64_t>(), es.odeg.as<uint32_t>(), n_own, nt,
+                                                           es.tile_shape.as<uint32_t>());
+  }
+  // the shares of the non-final first pass's tiles (byte model); a uniform tile of out-degree 0
+  // below bu_both_tiles -- which the class-ordered numbering rules out, and a stale numbering is
+  // not known to produce -- turns the shape words off for this edge space
+  void shape_shares() {
+    DevWords<unsigned long long, 4> sc;
+    sc.zero(c);
+    if (es.bu_both_tiles > 0)
+      k_shape_count<<<grid_for(es.bu_both_tiles), 256, 0, c.stream>>>(es.tile_shape.as<uint32_t>(), es.bu_both_tiles,
+                                                                      sc.dev());
+    const auto h = sc.read(c);
+    for (int k = 0; k < 3; k++) es.shape_tiles[k] = int64_t(h[size_t(k)]);
+    if (h[3]) {
+      es.tile_shape.release();
+      es.shape_tiles[0] = es.shape_tiles[1] = es.shape_tiles[2] = 0;
+    }
   }
   // exact row bounds of the bottom-up hops: past the last row with an in-edge nothing can be
   // found (final hop), past the last one with an in-edge and an out-edge nothing can extend
@@ -1056,9 +1125,11 @@ void build_transpose(Ctx& c, EdgeSpace& es) {
   b.hub_first_order();
   for (int h = 0; h < 2; h++) es.pair_col[h].release();
   es.tile_wide.release();
+  es.tile_shape.release();
   b.pack_quantised();
   b.pair_slab();
   b.live_bounds();
+  b.shape_shares();
   b.rest_records();
   NBG_HIP(hipStreamSynchronize(c.stream));
   NBG_HIP(hipGetLastError());

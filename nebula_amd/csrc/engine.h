@@ -386,6 +386,16 @@ struct EdgeSpace {
   // Built with the slab from the same row_ptr (exact whatever the numbering); one word of
   // padding past the last tile's word.
   DevBuf tile_wide;
+  // uint32 [tiles + 2], one word per 128-row slab tile, for the non-final first pass (k_bu_lean,
+  // option bu_lean_shape): bit 31 (kShapeWide) the tile's tile_wide bit; bits 0-30 the out-degree
+  // (odeg) that every row of the tile with an in-edge has (the others can never be found),
+  // kShapeMixed when they differ.  The two words
+  // past the last tile's read wide and mixed (the kernel asks for its next tile's word ahead).
+  // Built with the slab from the same row_ptr and odeg at every (re)build of the transpose; null
+  // (feature off for this edge space) when a tile below bu_both_tiles is uniform with degree 0.
+  // shape_tiles: uniform / two-slot / both, among the tiles below bu_both_tiles.
+  DevBuf tile_shape;
+  int64_t shape_tiles[3] = {0, 0, 0};
   // quantised predicate packing (bottom-up hops): the words of pair_col and tcol_q carry the
   // source gidx in their low q_gbits bits and, above it, q_bits bits of the bucket of transposed
   // prop q_field's value: bucket(v) = (v - q_min) * 2^q_bits / q_range (monotone), so a
@@ -420,6 +430,8 @@ struct EdgeSpace {
   bool kv_loaded = false;
 };
 constexpr int kRecEntries = 14;
+// EdgeSpace::tile_shape words
+constexpr uint32_t kShapeWide = 0x80000000u, kShapeMixed = 0x7fffffffu;
 
 // Vertex tag props: per tag, one row per vertex = the bytewise-first version under
 // the vertex key prefix (part, vid, tag) of the vid's own part -- what collectVertexProps reads

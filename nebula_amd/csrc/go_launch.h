@@ -82,7 +82,7 @@ struct BuLaunch {
   size_t ev_first = kNoEvent;  // timing event at the end of the first pass (the hop's kernel_ms)
   std::string k0, k1;          // rocprof names of the first-pass and the rest-pass kernel
   bool rest_rec = false;       // the rest pass read the rest records
-  uint64_t od_bytes = 0;       // out-degree bytes the first pass read (non-final hop)
+  uint64_t od_bytes = 0;       // out-degree bytes and tile_shape words the first pass read (non-final hop)
   uint64_t flag_bytes = 0;     // tile_wide bytes the first pass read (final hop, bu_fin_narrow)
 };
 // bottom-up hop: the first pass over the quad slab and the pending rows' rests; counters reduced

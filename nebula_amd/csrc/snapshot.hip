@@ -466,6 +466,7 @@ static void reset_transpose_derived(EdgeSpace& es) {
   es.q_gbits = es.q_bits = 0;
   for (int h = 0; h < 2; h++) es.pair_col[h].release();
   es.tile_wide.release();
+  es.tile_shape.release();
   es.odeg.release();
   es.odeg8.release();
   es.max_odeg = -1;
